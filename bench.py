@@ -1,15 +1,30 @@
 #!/usr/bin/env python3
-"""Headline benchmark: allreduce algbw (GB/s) + p50 latency of a 256 MiB bf16 gradient
-buffer per GPU (BASELINE.json metric; config "Ring allreduce of 256 MiB bf16 gradient
-buffer across 8xMI355X over xGMI"), one process per GPU.
+"""Headline benchmark: allreduce algbw (GB/s) of a 256 MiB bf16 gradient buffer per GPU
+(BASELINE.json metric; config "Ring allreduce of 256 MiB bf16 gradient buffer across
+8xMI355X over xGMI"), one process per GPU; with `--full` also its p50 latency, the
+validation against fp32 and every side section.
 
-    python bench.py                                    # 1 GPU, defaults
+    python bench.py                                    # 1 GPU, defaults: the headline only
+    python bench.py --full                             # ... and every side section below
+    python bench.py --dump-outputs DIR                 # ... and the last timed step's result
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 bench.py --gpus 8 --steps 20 --warmup 5
 
+A plain run sets up the engine, warms up, times `--steps` steps and prints the result line
+(`ms_per_step` = wall time of the timed steps / `--steps`). A plain one-GPU run validates
+nothing (`validated_max_abs_err` is null) and has no p50, comparison or side section: all of
+that runs with `--full` only. At N > 1 the bring-up validation, the candidate validation and
+the tuner choose the headline kernel, so they stay in the plain run, without the library
+comparison columns; how long that path takes outside its steps has been measured for
+`--gpus 1` only (a few seconds) - `--no-tune` gives a lean headline at N > 1.
+`--dump-outputs DIR` writes each rank's output buffer of the last timed step as float32 to
+DIR/allreduce_out_rank<k>.npy (a fixed seeded sample when it is large, `dump_indices`); the
+inputs are seeded, so two builds can be compared output for output.
+
 One "step" = one out-of-place allreduce of the buffer through the framework's engine
-(the fused xGMI two-shot kernel, csrc/hip/xgmi_comm.hip). The result is validated against
-an fp32 reference before timing. RCCL (`torch.distributed` nccl backend) is timed on the
-same buffer for comparison. Rank 0 prints ONE JSON line. `value` = algbw = buffer bytes / time
+(the fused xGMI two-shot kernel, csrc/hip/xgmi_comm.hip). With `--full` (and at N > 1) the
+result is validated against an fp32 reference before timing; with `--full` RCCL
+(`torch.distributed` nccl backend) is timed on the same buffer for comparison and a second,
+untimed pass of event pairs gives `p50_ms`. Rank 0 prints ONE JSON line. `value` = algbw = buffer bytes / time
 of the slowest rank (nccl-tests convention: the job reduces S bytes per step, whatever N), the
 figure RCCL's algbw column and BASELINE's metric use; `algbw_sum_over_ranks` = N x algbw is
 kept under its own key. At N=1 an allreduce is an out-of-place copy, so the N=1 point is an
@@ -17,11 +32,11 @@ HBM copy rate, not a communication rate (`algo` says "copy (world=1)" and the tu
 skipped); the `local_ranks` section then times the allreduce kernels themselves with 8
 logical ranks in one launch on the GPU. Data: synthetic uniform(-1, 1) gradients.
 
-Before anything is timed, every algorithm a section may pick (ll, one-shot, two-shot, ring,
+With `--full` (and at N > 1), before anything is timed, every algorithm a section may pick (ll, one-shot, two-shot, ring,
 threshold, all-to-all, all-gather, reduce-scatter) is checked against fp32 (`validated`),
-and rank 0 records the peer-access / link-type / hop matrix (`topology`).
+and (`--full` only) rank 0 records the peer-access / link-type / hop matrix (`topology`).
 
-After the headline, side sections on the same engine (in the JSON, not in `value`): the
+With `--full`, after the headline, side sections on the same engine (in the JSON, not in `value`): the
 tuner's size sweep vs RCCL, the straggler-tolerant kernel, all-to-all / all-gather /
 reduce-scatter, the fused sharded AdamW step, and `dp` = BASELINE configs 4 and 5 (one
 data-parallel step of the ResNet-50 and full Llama-3-8B gradient sets with a GEMM-backed
@@ -73,6 +88,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from akka_allreduce_1_amd.ops import fill_uniform  # noqa: E402
 from akka_allreduce_1_amd.parallel.comm import LOSSY_ALGOS, CommError, XgmiCommunicator, init_distributed  # noqa: E402
+from benchmarks.outputs import dump_outputs  # noqa: E402
 from benchmarks.summary import headline_guard  # noqa: E402
 from akka_allreduce_1_amd.utils.timing import busbw, percentile  # noqa: E402
 
@@ -729,6 +745,13 @@ def emit(rank: int, result: dict) -> bool:
         return True
 
 
+def finish(rank: int, result: dict) -> None:
+    """The one way out of a run that reached its result: the line, then the group's teardown."""
+    emit(rank, result)
+    dist.barrier()
+    dist.destroy_process_group()
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -769,12 +792,22 @@ def main() -> None:
     ap.add_argument("--share-device", action="store_true",
                     help="rehearsal: every rank on cuda:0 over gloo (RCCL refuses two ranks on one GPU), "
                          "workgroup budget split between the ranks so all spinning workgroups stay resident")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every side section (validation against fp32, p50 pass, RCCL and "
+                         "kernel comparisons, size axis, protocol, stragglers, DP steps); off: headline only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned to DIR/allreduce_out_rank<k>.npy (float32; a "
+                         "fixed seeded sample of a large buffer)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank, world, local = init_distributed("gloo" if args.share_device else "nccl")
     if rank == 0:
         _DETAIL["path"] = (os.path.join("gpurun_out", f"bench_detail_n{world}.json") if args.detail_out is None
                            else args.detail_out or None)
+        if not args.full and args.detail_out is None:
+            _DETAIL["path"] = None  # a plain run writes no side file unless asked to
     if world != args.gpus:
         log(rank, f"warning: --gpus {args.gpus} but WORLD_SIZE={world}; using {world}")
     grid = 0
@@ -791,7 +824,11 @@ def main() -> None:
 
     # ---- engine bring-up + validation; any failure degrades to RCCL (recorded) instead of
     # losing the run
-    comm, reason, err = None, "", float("nan")
+    # A plain one-GPU run times the headline only: every algorithm is the same out-of-place copy
+    # there, so nothing is chosen by a validated candidate list. At N > 1 the checks and the tuner
+    # below choose the headline kernel and stay in the plain run.
+    checked = args.full or world > 1
+    comm, reason, err = None, "", float("nan") if checked else None
     t_setup = time.perf_counter()
     log(rank, f"bring-up: world={world} slot={slot >> 20} MiB")
     try:
@@ -799,10 +836,11 @@ def main() -> None:
         # (the lock-step kernels use slab row 0 only; the extra rows cost HBM, not time)
         comm = XgmiCommunicator(slot_bytes=slot, grid=grid, max_lag=1 if world > 1 else None)
         log(rank, f"{comm}  tensor={args.size_mib} MiB {args.dtype}  (setup {time.perf_counter() - t_setup:.1f} s)")
-        ok, err = validate(comm, n, dtype, dev, rank, world)
-        ok_small, err_small = validate(comm, 12345, dtype, dev, rank, world)
-        if not (ok and ok_small):
-            reason = f"validation failed (max err {err:.3g} / {err_small:.3g})"
+        if checked:
+            ok, err = validate(comm, n, dtype, dev, rank, world)
+            ok_small, err_small = validate(comm, 12345, dtype, dev, rank, world)
+            if not (ok and ok_small):
+                reason = f"validation failed (max err {err:.3g} / {err_small:.3g})"
     except Exception as e:  # noqa: BLE001 - reported in the JSON
         reason = f"engine unavailable: {e!r}"
     healthy = torch.tensor([0 if reason else 1], device=dev)
@@ -822,7 +860,7 @@ def main() -> None:
         dist.all_reduce(y)
 
     validated = None
-    if engine_ok:
+    if engine_ok and checked:
         log(rank, "validating every algorithm against fp32")
         # every algorithm a section or the tuner may pick, against fp32, before any timing
         validated = validate_algos(comm, dtype, dev, rank, world)
@@ -837,7 +875,7 @@ def main() -> None:
                 engine_ok, reason = False, f"reset after failed validation: {e!r}"
     ok_algos = {k for k, v in (validated or {}).items() if v["validated"]}
     links = None
-    if engine_ok and world > 1 and not args.no_links:
+    if engine_ok and args.full and world > 1 and not args.no_links:
         # the xGMI bring-up pack, before anything else is timed: per-link push rate, all-peer
         # fan-out rate and flag hand-off latency on the engine's own store path
         # (akka_allreduce_1_amd/utils/links.py), so a slow first multi-GPU run is attributable
@@ -856,7 +894,7 @@ def main() -> None:
     if engine_ok and not args.no_tune and world > 1:  # at world = 1 every candidate is the same copy
         # RCCL / RS+AG are timed as comparison columns (rccl_p50_us, speedup_vs_rccl per size):
         # tune() never adopts a library path, so the headline is always this engine's kernel
-        lib = () if args.no_rccl else ("rccl", "rsag")
+        lib = ("rccl", "rsag") if args.full and not args.no_rccl else ()
         cands = tuple(c for c in ("ll", "oneshot", "twoshot", "ring", "ring_native", "threshold") if c in ok_algos) + lib
         sweep = comm.tune(max_bytes=nbytes, dtype=dtype, iters=args.sweep_steps, candidates=cands,
                           grids=(128, 256))
@@ -901,7 +939,9 @@ def main() -> None:
     for _ in range(args.warmup):
         step()
     wall = timed(step, args.steps, dev)
-    per = event_times(step, args.steps, dev)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, y, rank, world)
+    per = event_times(step, args.steps, dev) if args.full else None  # p50: an untimed pass of its own
     if engine_ok:
         try:
             comm.check()
@@ -911,7 +951,6 @@ def main() -> None:
     wall = max_over_ranks(wall, dev)
     ms = wall / args.steps * 1e3
     algbw = nbytes / (ms / 1e3) / 1e9
-    p50 = max_over_ranks(percentile(per, 50), dev)
 
     result = {
         "metric": "allreduce_algbw",
@@ -940,19 +979,21 @@ def main() -> None:
             "wire": ("element type per hop (rounded P-1 times)" if chosen.split("@")[0] in LOSSY_ALGOS
                      else "fp32 accumulation, rounded once" if args.dtype == "bf16" else "fp32"),
         },
-        "p50_ms": round(p50, 4),
         "busbw": round(busbw(algbw, world), 2),
         "validated_max_abs_err": err,
         "engine_ok": engine_ok,
         "status": status,
     }
+    if per is not None:
+        result["p50_ms"] = round(max_over_ranks(percentile(per, 50), dev), 4)
     if world == 1:
         result["value_note"] += ("; world=1: the allreduce is an out-of-place HBM copy (no communication) - "
-                                 "see local_ranks for the allreduce kernels on this GPU")
+                                 + ("see local_ranks for the allreduce kernels on this GPU" if args.full else
+                                    "--full adds local_ranks, the allreduce kernels on this GPU"))
     if validated is not None:
         result["validated"] = {k: v["validated"] for k, v in validated.items()}
         result["validation"] = validated
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             result["topology"] = topology(world)
         except Exception as e:  # noqa: BLE001
@@ -961,6 +1002,11 @@ def main() -> None:
         result["engine_note"] = reason
     if links is not None:
         result["xgmi_links"] = links
+    if sweep is not None:
+        result["sweep"] = sweep
+    if not args.full:  # a plain run ends here: every section below is a measurement of its own
+        finish(rank, result)
+        return
 
     if engine_ok and not chosen.startswith("twoshot") and world > 1:
         for _ in range(args.warmup):
@@ -1042,8 +1088,6 @@ def main() -> None:
                           "errors": [r.get("error") for r in rows if r.get("error")][:2]}
         if ok:
             mark_xdev_validated()
-    if sweep is not None:
-        result["sweep"] = sweep
     if engine_ok and world == 1 and not args.share_device and not args.no_local:
         # the allreduce kernels at N = 1: 8 logical ranks in one launch on this GPU
         log(rank, "local_ranks: 8 logical ranks in one launch")
@@ -1130,9 +1174,7 @@ def main() -> None:
             return
         result["dp"] = dp
 
-    emit(rank, result)
-    dist.barrier()
-    dist.destroy_process_group()
+    finish(rank, result)
 
 
 if __name__ == "__main__":

@@ -4,7 +4,6 @@ import pytest
 
 from akka_allreduce_1_amd import config as mc
 
-REF_CONF = "/root/reference/src/main/resources/application.conf"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -20,14 +19,46 @@ def test_parse_hocon_subset():
     assert flat == {"a.b": 1, "a.c": "x y", "a.d.e": [1, 2, "three"], "a.f": True, "g": "10s"}
 
 
-@pytest.mark.skipif(not os.path.exists(REF_CONF), reason="reference config not mounted")
-def test_reference_application_conf_is_accepted():
-    cfg = mc.Config().load_file(REF_CONF)
-    assert cfg["mxar.remote.hostname"] == "127.0.0.1"
-    assert cfg["mxar.remote.port"] == 0
-    assert cfg.seeds() == ["akka.tcp://ClusterSystem@127.0.0.1:2551", "akka.tcp://ClusterSystem@127.0.0.1:2552"]
-    assert cfg["mxar.cluster.auto-down-unreachable-after"] == 10.0
-    assert cfg["mxar.loglevel"] == "INFO" and cfg["mxar.log-dead-letters"] == 5
+# An Akka deployment's application.conf as an Akka user would write one (Akka's public setting
+# names; layout and values are this project's own): nested and dotted `akka.*` keys, a foreign
+# section, a list over two lines, durations, a ${user.dir} substitution.
+AKKA_CONF = '''
+akka.loglevel = "WARNING"
+akka {
+  log-dead-letters = 3
+  actor.provider = cluster          // foreign to this engine: ignored
+  remote.netty.tcp {
+    hostname = "10.1.2.3"
+    port = 2700
+  }
+  cluster {
+    roles = [worker]
+    seed-nodes = ["akka.tcp://Grads@10.1.2.3:2700",
+                  "akka.tcp://Grads@10.1.2.4:2700", "akka.tcp://Grads@10.1.2.5:2700"]
+    auto-down-unreachable-after = 2500ms
+    failure-detector { heartbeat-interval = 2s, acceptable-heartbeat-pause = 7s }
+  }
+}
+# extension settings of the JVM side, with a substitution
+akka.extensions = ["akka.cluster.metrics.ClusterMetricsExtension"]
+akka.cluster.metrics.native-library-extract-folder = ${user.dir}/native
+'''
+
+
+def test_akka_namespaced_conf_is_accepted(tmp_path):
+    path = tmp_path / "application.conf"
+    path.write_text(AKKA_CONF)
+    cfg = mc.Config().load_file(str(path))
+    assert cfg["mxar.remote.hostname"] == "10.1.2.3"
+    assert cfg["mxar.remote.port"] == 2700
+    assert cfg.seeds() == ["akka.tcp://Grads@10.1.2.3:2700", "akka.tcp://Grads@10.1.2.4:2700",
+                           "akka.tcp://Grads@10.1.2.5:2700"]
+    assert cfg["mxar.cluster.roles"] == ["worker"]
+    assert cfg["mxar.cluster.auto-down-unreachable-after"] == 2.5
+    assert cfg["mxar.cluster.failure-detector.heartbeat-interval"] == 2.0
+    assert cfg["mxar.cluster.failure-detector.acceptable-heartbeat-pause"] == 7.0
+    assert cfg["mxar.loglevel"] == "WARNING" and cfg["mxar.log-dead-letters"] == 3
+    assert cfg["mxar.allreduce.th-reduce"] == 0.9  # untouched defaults stay
 
 
 def test_own_conf_and_layering():

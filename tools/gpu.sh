@@ -34,7 +34,7 @@ tests() {
 }
 
 bench() {
-  timeout -k 10 900 python -u bench.py "$@" > $O/bench_n1.json 2> $O/bench_n1.err
+  timeout -k 10 900 python -u bench.py --full "$@" > $O/bench_n1.json 2> $O/bench_n1.err
   local rc=$?
   echo "bench rc=$rc"
   [ $rc -eq 0 ] || tail -20 $O/bench_n1.err
@@ -53,7 +53,7 @@ case $task in
   bench) bench "$@" ;;
   prof)
     # (no native-deployment section: its child processes would run under the profiler too)
-    timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- python3 bench.py --no-native "$@" \
+    timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- python3 bench.py --full --no-native "$@" \
       > $O/prof_bench.json 2> $O/prof_bench.err
     rc=$?
     f=$(find $O/prof -name '*kernel_stats.csv' | head -1)
@@ -78,7 +78,7 @@ case $task in
     [ ${#ns[@]} -eq 0 ] && ns=(2 4 8)
     for n in "${ns[@]}"; do
       timeout -k 10 400 python -u -m torch.distributed.run --nproc-per-node $n --master-addr 127.0.0.1 \
-        --master-port $((29640 + n)) bench.py --gpus $n --share-device --no-dp --steps 10 --warmup 3 \
+        --master-port $((29640 + n)) bench.py --full --gpus $n --share-device --no-dp --steps 10 --warmup 3 \
         > $O/rehearsal_n$n.json 2> $O/rehearsal_n$n.err
       rc=$?
       echo "rehearsal n=$n rc=$rc"
