@@ -209,6 +209,18 @@ static hipStream_t as_stream(uintptr_t s) { return reinterpret_cast<hipStream_t>
 static const void* as_cptr(uintptr_t p) { return reinterpret_cast<const void*>(p); }
 static void* as_ptr(uintptr_t p) { return reinterpret_cast<void*>(p); }
 
+static py::dict geometry_dict(const LaunchGeometry& g) {
+  py::dict d;
+  d["block"] = g.block;
+  d["chunk"] = g.chunk;
+  d["subchunk"] = g.subchunk;
+  d["nch"] = g.nch;
+  d["sub"] = g.sub;
+  d["sgroup"] = g.sgroup;
+  d["gx"] = g.gx;
+  return d;
+}
+
 void bind_hip(py::module_& m) {
   py::module_ h = m.def_submodule("hip", "HIP/CDNA4 data plane (gfx950)");
   register_device_payload_hooks(&device_payload_to_py, &py_to_device_payload);
@@ -254,7 +266,93 @@ void bind_hip(py::module_& m) {
         "workgroups per rank at most when several logical ranks share one default-grid launch (0: no cap)");
   h.def("size_grid_rule", &size_grid_rule, py::arg("bytes"), py::arg("grid"), py::arg("world"), py::arg("oneshot"),
         py::arg("full_at") = int64_t{512} << 20, py::arg("cap") = 256,
-        "workgroups a default-grid launch of `bytes` (all ranks of the launch) uses (XgmiComm::launch_grid)");
+        "workgroups a default-grid launch of `bytes` (all ranks of the launch) uses (launch_grid)");
+  // the pure launch planner (csrc/runtime/launch_geometry.h): no GPU needed
+  py::class_<GridKnobs>(h, "GridKnobs")
+      .def(py::init<>())
+      .def_readwrite("world", &GridKnobs::world)
+      .def_readwrite("rows", &GridKnobs::rows)
+      .def_readwrite("grid", &GridKnobs::grid)
+      .def_readwrite("default_grid", &GridKnobs::default_grid)
+      .def_readwrite("size_grid", &GridKnobs::size_grid)
+      .def_readwrite("maxch", &GridKnobs::maxch)
+      .def_readwrite("slot_bytes", &GridKnobs::slot_bytes)
+      .def_readwrite("units_per_wg", &GridKnobs::units_per_wg)
+      .def_readwrite("sub_max", &GridKnobs::sub_max)
+      .def_readwrite("geom", &GridKnobs::geom)
+      .def_readwrite("flat_min", &GridKnobs::flat_min)
+      .def_readwrite("ring_depth", &GridKnobs::ring_depth)
+      .def_readwrite("ring_grid", &GridKnobs::ring_grid)
+      .def_readwrite("th_oneshot_max", &GridKnobs::th_oneshot_max)
+      .def_readwrite("no_gate_shortcut", &GridKnobs::no_gate_shortcut);
+  h.def(
+      "plan_allreduce",
+      [](const std::string& kind, const GridKnobs& k, int64_t n, int64_t es, int ranks_here) {
+        const bool adamw = kind == "adamw";
+        const Algo algo = kind == "ll" ? Algo::LL : kind == "oneshot" ? Algo::OneShot : kind == "ring" ? Algo::Ring
+                          : kind == "ring_native"                     ? Algo::RingNative
+                                                                      : Algo::TwoShot;
+        if (!adamw && algo == Algo::TwoShot && kind != "twoshot")
+          throw std::invalid_argument("plan_allreduce: kind is ll, oneshot, twoshot, ring, ring_native or adamw");
+        return geometry_dict(plan_allreduce(algo, k, n, es, ranks_here, adamw));
+      },
+      py::arg("kind"), py::arg("knobs"), py::arg("n"), py::arg("elem_size"), py::arg("ranks_here") = 1,
+      "geometry of one allreduce segment of n elements: block, chunk, subchunk, nch, sub, sgroup, gx");
+  h.def(
+      "plan_coll",
+      [](const std::string& op, const GridKnobs& k, int64_t n, int64_t es, int ranks_here) {
+        const int code = op == "all_to_all" ? 0 : op == "all_gather" ? 1 : op == "reduce_scatter" ? 2 : -1;
+        if (code < 0) throw std::invalid_argument("plan_coll: op is all_to_all, all_gather or reduce_scatter");
+        py::dict d = geometry_dict(plan_coll(static_cast<Coll>(code), k, n, es, ranks_here));
+        d.attr("pop")("block");  // the caller's m
+        return d;
+      },
+      py::arg("op"), py::arg("knobs"), py::arg("n"), py::arg("elem_size"), py::arg("ranks_here") = 1,
+      "geometry of one collective segment of n elements per block");
+  h.def(
+      "plan_threshold",
+      [](const GridKnobs& k, int64_t n, int64_t es, int ranks_here, float thr, float thc, int64_t block, int64_t chunk,
+         bool order_ref, bool split, bool lag_skip) {
+        RoundShape spec;
+        spec.block = block;
+        spec.chunk = chunk;
+        spec.order_ref = order_ref;
+        spec.split = split;
+        spec.lag_skip = lag_skip;
+        const ThresholdPlan p = plan_threshold(k, n, es, ranks_here, thr, thc, spec);
+        py::dict d = geometry_dict(p);
+        d["min_reduce"] = p.min_reduce;
+        d["min_complete"] = p.min_complete;
+        d["full"] = p.full;
+        d["gate_shortcut"] = p.gate_shortcut;
+        d["oneshot"] = p.oneshot;
+        d["lag_skip"] = p.lag_skip;
+        d["split"] = p.split ? 1 : 0;
+        return d;
+      },
+      py::arg("knobs"), py::arg("n"), py::arg("elem_size"), py::arg("ranks_here") = 1, py::arg("th_reduce") = 1.f,
+      py::arg("th_complete") = 1.f, py::arg("block") = 0, py::arg("chunk") = 0, py::arg("order_ref") = false,
+      py::arg("split") = false, py::arg("lag_skip") = false,
+      "geometry, thresholds and kernel body of one threshold round (block > 0: a protocol round's RoundSpec)");
+  h.def(
+      "slab_layout",
+      [](int world, int64_t slot_bytes, int threshold_rows, int64_t min_flag_bytes, int64_t flag_gran, int64_t ll_max) {
+        const SlabLayout L = slab_layout(world, slot_bytes, threshold_rows, min_flag_bytes, flag_gran, ll_max);
+        py::dict d;
+        d["slot_bytes"] = L.slot_bytes;
+        d["slot_stride"] = L.slot_stride;
+        d["maxch"] = L.maxch;
+        d["off_S"] = L.off_S;
+        d["off_R"] = L.off_R;
+        d["off_LL"] = L.off_LL;
+        d["ll_max"] = L.ll_max;
+        d["ll_slot"] = L.ll_slot;
+        d["slab_bytes"] = L.slab_bytes;
+        d["alloc_bytes"] = L.alloc_bytes;
+        return d;
+      },
+      py::arg("world"), py::arg("slot_bytes"), py::arg("threshold_rows") = 0, py::arg("min_flag_bytes") = 0,
+      py::arg("flag_gran") = 0, py::arg("ll_max") = 512 * 1024, "slab offsets and sizes, without allocating");
   py::enum_<DType>(h, "DType").value("F32", DType::F32).value("BF16", DType::BF16).value("F16", DType::F16);
 
   py::class_<XgmiPlaneStats>(h, "XgmiPlaneStats")

@@ -28,17 +28,13 @@
 #include <memory>
 #include <vector>
 
+#include "../runtime/launch_geometry.h"
+#include "comm_args.h"
+
 namespace mxar {
 
 enum class DType : int { F32 = 0, BF16 = 1, F16 = 2 };
 inline size_t dtype_size(DType d) { return d == DType::F32 ? 4 : 2; }
-
-// Ring: fp32 partials on the reduce-scatter hops (rounded once); RingNative: partials in the
-// element type (half the RS wire bytes for 16-bit types, one rounding per hop).
-enum class Algo : int { Auto = 0, TwoShot = 1, OneShot = 2, Ring = 3, LL = 4, RingNative = 5 };
-
-// The reference's two allreduce phases as collectives of their own (xgmi_coll.hip).
-enum class Coll : int { AllToAll = 0, AllGather = 1, ReduceScatter = 2 };
 
 // AdamW hyper-parameters of one fused step (PyTorch AdamW semantics; step counts from 1).
 struct AdamW {
@@ -52,82 +48,6 @@ struct AdamShard {
   float* exp_avg = nullptr;
   float* exp_avg_sq = nullptr;
 };
-
-constexpr int kMaxRanks = 16;
-// threshold kernel one-shot body: ranks at most (its per-source registers; larger memberships
-// take the two-shot body)
-constexpr int kOneshotRanks = 8;
-// Threshold kernel: gather units (chunk x peer) one workgroup may own (its pending bitmap in
-// LDS), and reduce chunks per workgroup with a launch snapshot (reference arrival order).
-constexpr int kThresholdGatherUnits = 4096;
-constexpr int kThresholdSnapChunks = 2048;
-constexpr int kCommThreads = 256;
-
-// Resident rounds (xgmi_threshold.hip threshold_resident_kernel; xgmi_plane.cc): the host
-// posts each round as one 64-B entry of a door ring in pinned host memory, the sequence word
-// written last; a kernel that stays on the GPU between rounds runs them.
-struct ResidentDoor {
-  uint64_t in, out, counts, counts_host, err_out, done_out;  // device-visible addresses
-  uint32_t epoch;
-  int32_t cmd;  // kResRound / kResCold / kResStop
-  uint32_t seq;
-  uint32_t check;  // door_check(entry): the kernel reads the whole entry in one 64-B load and
-                   // takes it only when the check matches (no second read after the sequence word)
-};
-constexpr int kResidentDoors = 64;
-// A mix of the entry's words and its sequence number (host and device compute the same).
-#if defined(__HIPCC__)
-__host__ __device__
-#endif
-inline uint32_t door_check(const uint32_t* w14, uint32_t seq) {
-  uint32_t h = seq * 0x9E3779B1u + 0x7F4A7C15u;
-  for (int i = 0; i < 14; ++i) {
-    h = (h ^ w14[i]) * 0x85EBCA6Bu;
-    h ^= h >> 13;
-  }
-  return h ^ (h >> 16);
-}
-enum : int32_t { kResRound = 0, kResCold = 1, kResStop = 2 };
-// host state words the kernel writes: [0] kResRunning / kResExiting / kResExited, [1] the
-// last entry it consumed (its door slot may be reused)
-enum : uint32_t { kResRunning = 0, kResExiting = 1, kResExited = 2 };
-
-// Group resident rounds (xgmi_threshold.hip threshold_group_resident_kernel; xgmi_plane.cc
-// PlaneGroup): the co-located workers of one job share ONE resident kernel, a slice of
-// workgroups per worker, each fed from that worker's own door ring by a dispatcher wave.
-struct GroupResidentMember {
-  const ResidentDoor* door;  // the worker's pinned door ring (device-visible address)
-  uint32_t* hstate;          // its pinned words: [1] the last entry consumed
-  uint64_t* dm;              // its device words: [0] go, [2..9] the entry handed to its slice
-  const uint32_t* hforce;    // its pinned force / abort words
-  const uint32_t* habort;
-  uint64_t* stamps;          // its phase-stamp buffer (study knob; null = off)
-  uint64_t* split_dec;       // its split-chunk scratch (RoundSpec::split_scratch; null = unsplit)
-  uint32_t* split_ctr;
-  uint32_t* split_early;
-  uint32_t seq0;             // the first entry this launch takes
-  int rank;
-};
-
-// The launch-size grid rule (XgmiComm::launch_grid; profiles/round4/README.md section 9):
-// workgroups for a launch moving `bytes` of input over all its ranks at device grid `grid`.
-// Two-shot style: one per 64 KiB, 64..`cap`, the full grid from `full_at`; one-shot: every
-// rank reads all `world` inputs, so one per 64 KiB of world x bytes, 64..the full grid.
-inline int size_grid_rule(int64_t bytes, int grid, int world, bool oneshot, int64_t full_at = int64_t{512} << 20,
-                          int64_t cap = 256) {
-  if (oneshot) bytes *= (world > 1 ? world : 1);
-  else if (bytes >= full_at) return grid;
-  int64_t g = bytes / (int64_t{64} << 10);
-  const int64_t hi = oneshot ? grid : cap;
-  g = g < 64 ? 64 : (g > hi ? hi : g);
-  return static_cast<int>(g < grid ? g : grid);
-}
-
-// Workgroups per rank at most when `ranks_here` logical ranks share one launch at the default
-// grid (XgmiComm::shared_launch_cap): a quarter of that grid, half the CUs. 0 = no cap.
-inline int shared_launch_rule(int ranks_here, int default_grid) {
-  return ranks_here <= 1 ? 0 : (default_grid / 4 > 1 ? default_grid / 4 : 1);
-}
 
 struct CommStats {
   uint64_t calls = 0, launches = 0, bytes = 0, oneshot = 0, twoshot = 0, ring = 0, threshold = 0, ll = 0, coll = 0,
@@ -172,10 +92,7 @@ class XgmiComm {
   void connect_ptrs(const std::vector<char*>& bases);
 
   // Slab geometry for (world, slot_bytes, threshold_rows), without allocating.
-  struct Layout {
-    int64_t slot_bytes = 0, slot_stride = 0, maxch = 0, off_S = 0, off_R = 0, off_LL = 0, ll_max = 0, ll_slot = 0;
-    int64_t slab_bytes = 0, alloc_bytes = 0;
-  };
+  using Layout = SlabLayout;
   static Layout layout(int world, int64_t slot_bytes, int threshold_rows, int64_t min_flag_bytes = 0,
                        int64_t flag_gran = 0);
   // Bytes of the flag table alone (the part of off_S before its 64 KiB rounding).
@@ -252,7 +169,7 @@ class XgmiComm {
   // from entry `seq` on (launch_resident; hstate / dm: the state words above, and 32 device
   // words of scratch). Per-round operands come from the entries, not from `spec`.
   struct ResidentPlan {
-    std::shared_ptr<void> args;  // the kernel's CommArgs
+    std::shared_ptr<const CommArgs> args;  // the kernel's arguments
     int grid = 0;
     DType dt = DType::F32;
     int64_t n = 0;
@@ -272,6 +189,8 @@ class XgmiComm {
   static void launch_group_resident(const std::vector<XgmiComm*>& comms, const std::vector<const ResidentPlan*>& plans,
                                     const std::vector<GroupResidentMember>& members, uint32_t* gstate, uint64_t* gdm,
                                     uint32_t gen, uint64_t idle_ticks, hipStream_t stream);
+  // What the geometry rules read from this communicator (launch_geometry.h).
+  GridKnobs knobs() const;
   // Workgroups a round launch of `nch` chunks per block uses (counts / geometry checks).
   int round_grid(int nch) const;
   // Workgroups per rank at most when several ranks share one launch (default grid only).
@@ -401,7 +320,7 @@ class XgmiComm {
   uint32_t* ctl_ptr() const { return ctl_; }  // device control words ([2] = error word)
   int64_t slab_bytes() const { return slab_bytes_; }
   int64_t alloc_bytes() const { return alloc_bytes_; }
-  static int64_t min_chunk_bytes() { return 1024; }
+  static int64_t min_chunk_bytes() { return mxar::min_chunk_bytes(); }
 
  private:
   // Stream safety: every launch of a communicator reads its epoch / slab rows from device
@@ -421,15 +340,20 @@ class XgmiComm {
 
   static void run_coll(const std::vector<XgmiComm*>& group, Coll op, const std::vector<const void*>& ins,
                        const std::vector<void*>& outs, int64_t m, DType dt, hipStream_t stream, float scale);
+  // The fields every launch of `group` shares: membership, slab layout, timeout, fence, peers.
+  CommArgs base_args(const std::vector<XgmiComm*>& group) const;
+  // A grouped launch: connected, consecutive ranks on one device (need_rows: and one lag ring
+  // depth), one 16-byte aligned input and output per rank.
+  static void check_group(const std::vector<XgmiComm*>& group, const std::vector<const void*>& ins,
+                          const std::vector<void*>& outs, bool need_rows = false);
   // run_threshold's launch arguments and grid (no launch); false: nothing to do (n <= 0)
   static bool threshold_args(const std::vector<XgmiComm*>& group, const std::vector<const void*>& ins,
                              const std::vector<void*>& outs, int64_t n, DType dt, float thr, float thc,
-                             int32_t* counts, float scale, bool rescale, const RoundSpec* spec, void* args, int* gx);
+                             int32_t* counts, float scale, bool rescale, const RoundSpec* spec, CommArgs& args,
+                             int* gx);
   static void run_threshold(const std::vector<XgmiComm*>& group, const std::vector<const void*>& ins,
                             const std::vector<void*>& outs, int64_t n, DType dt, hipStream_t stream, float thr,
                             float thc, int32_t* counts, float scale, bool rescale, const RoundSpec* spec = nullptr);
-  void geometry_threshold(int64_t n, DType dt, int ranks_here, int64_t* block, int64_t* chunk, int* nch,
-                          int* gx) const;
 
   int rank_, world_, device_, grid_, rows_;
   char* probe_coarse_ = nullptr;  // this rank's coarse-grained probe buffer (xgmi_probe.hip)
@@ -449,16 +373,15 @@ class XgmiComm {
   int fence_ = 3;
   uint64_t* stamps_ = nullptr;  // phase-stamp buffer (study knob, set_phase_stamps)
   int64_t stamp_slots_ = 0;
-  int units_per_wg_ = 0;  // two-shot scatter units per workgroup; 0 = by block size (launch_segment)
+  int units_per_wg_ = 0;  // two-shot scatter units per workgroup; 0 = by block size (plan_twoshot)
   int sub_max_ = 0;       // two-shot: most reduce pieces per chunk; 0 = by block size
   int ring_depth_ = 1;    // ring: chunks per workgroup, walked step-major (MXAR_RING_DEPTH)
   int ring_grid_ = 256;
   // The device-default grid, and whether a launch at the default grid sizes it by its bytes
-  // (launch_grid; MXAR_SIZE_GRID=0: always the full grid). An explicit grid (set_grid(g),
-  // tune()'s "algo@g" labels) is always used as given.
+  // (launch_grid, launch_geometry.h; MXAR_SIZE_GRID=0: always the full grid). An explicit grid
+  // (set_grid(g), tune()'s "algo@g" labels) is always used as given.
   int default_grid_ = 0;
   bool size_grid_ = true;
-  int launch_grid(int64_t bytes_in_launch, bool oneshot, int64_t full_at = int64_t{512} << 20) const;
   char* slab_ = nullptr;            // own fine-grained slab (flags | S | R | LL)
   uint32_t* ctl_ = nullptr;         // [0] epoch, [1] ticket, [2] sticky error (device memory)
   char* peers_[kMaxRanks] = {};     // slab base of every rank (own included)
@@ -469,10 +392,7 @@ class XgmiComm {
   bool noguard_ = false;           // MXAR_SLOT_GUARD=0 (study / negative control only)
   bool no_gate_shortcut_ = false;  // MXAR_STUDY=1 MXAR_GATE_SHORTCUT=0: threshold lag gate always polled (A/B)
   // full-threshold rounds of at most this many bytes per rank run the one-shot body
-  // (xgmi_threshold.hip; MXAR_STUDY=1 MXAR_TH_ONESHOT_MAX=bytes, 0 = off): 1.1-1.8x faster
-  // than the two-shot body at 64-256 KiB (profiles/round6 section 12). The multi-process
-  // failures of a first 256 KiB default came from workgroups past the fast pass; the host now
-  // sizes the grid for it or takes the two-shot body (threshold_args)
+  // (GridKnobs::th_oneshot_max; MXAR_STUDY=1 MXAR_TH_ONESHOT_MAX=bytes, 0 = off)
   int64_t th_oneshot_max_ = 256 << 10;
   bool ring_hop_rows_ = false;     // negative control: the two-writer ring flag layout (MXAR_RING_FLAGS=hop)
   int geom_ = -1;                  // two-shot geometry: -1 by block size, 0 coarse, 1 fine, 2 flat (MXAR_TWOSHOT_GEOM)

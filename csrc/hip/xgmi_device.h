@@ -5,120 +5,13 @@
 
 #include <hip/hip_runtime.h>
 
+#include "comm_args.h"
 #include "device_common.h"
 #include "xgmi_comm.h"
+#include "xgmi_launch.h"
 
 namespace mxar {
 using namespace dev;
-
-// One launch serves one rank (one process per GPU: gridDim.y == 1, rank = rank0) or all
-// P logical ranks of a single-process cluster on one device (gridDim.y == P, rank =
-// rank0 + blockIdx.y): every rank's workgroups are then co-resident in ONE dispatch, so
-// no rank can be starved behind another on a shared hardware queue.
-struct CommArgs {
-  const char* in[kMaxRanks];
-  char* out[kMaxRanks];
-  // per rank: [0] epoch [1] ticket [2] error; threshold rounds: [3] completion / late-ticket
-  // counter [4] round count [5] early arrivals [6] snapshot barrier [7] early tickets
-  uint32_t* ctl[kMaxRanks];
-  int64_t n;      // elements in this segment
-  int64_t block;  // elements per block (two-shot) / whole segment (one-shot)
-  int64_t chunk;  // elements per chunk (scatter / gather work unit)
-  int64_t subchunk;  // elements per reduce work unit (chunk split `sub` ways)
-  int nch;        // chunks per block
-  int sub;        // reduce units per chunk
-  int P;
-  int rank0;
-  int fence;      // bit0: system release before flags, bit1: system acquire after waits
-  float scale;    // applied to the fp32 sum before rounding (1 = sum, 1/P = mean)
-  int64_t maxch;
-  int64_t off_S, off_R, slot_bytes;  // slot_bytes: the slot STRIDE in the slab (capacity + pad)
-  int64_t slot_cap;                   // usable bytes per slot
-  uint64_t timeout;
-  char* base[kMaxRanks];
-  // threshold kernel (xgmi_threshold.hip); rows = 1 for the other kernels
-  int rows;            // S/R slot rows in the slab: row 0 (lock-step kernels) + trows
-  int trows;           // threshold lag ring: rows 1..trows (maxLag + 1; 0 = not allocated)
-  int full;            // thReduce = thComplete = 1: every contribution and chunk is taken
-  int min_reduce;      // contributions per chunk that complete a reduce (thReduce)
-  int64_t min_complete;  // reduced chunks that complete the round (thComplete)
-  int32_t* counts;     // optional [P][nch] contributions per output chunk (0 = missing)
-  int rescale;         // scale a chunk reduced from cnt contributions by P / cnt
-  // protocol-engine rounds (xgmi_plane.cc, RoundSpec): explicit round epoch (0 = ctl[4] + 1),
-  // forced-cold round (no own contribution, nothing waited for), the reference's
-  // arrival-order accounting, and the pinned host word the engine raises on a catch-up
-  uint32_t epoch_set;
-  int cold;
-  int order_ref;
-  const uint32_t* hforce;
-  const uint32_t* habort;  // pinned host word: rounds <= this epoch are abandoned (threshold kernel)
-  uint32_t* err_out;  // optional: the round's error word, written by the last workgroup (pinned host)
-  uint32_t* done_out;  // optional: set to the epoch by the last workgroup after its release (pinned host)
-  // optional: where the last workgroup copies `counts` (P x nch int32, pinned host) once the
-  // round is done - every workgroup writes its counts to device memory (`counts`), so no
-  // unit waits on a PCIe write acknowledgement
-  int32_t* counts_host;
-  // low-latency one-shot (xgmi_ll.hip): slots [parity][src] of ll_slot bytes at off_LL
-  int64_t off_LL, ll_slot;
-  // fused reduce-scatter + AdamW + all-gather (xgmi_adam.hip): per rank fp32 shard state
-  float* opt_p[kMaxRanks];
-  float* opt_m[kMaxRanks];
-  float* opt_v[kMaxRanks];
-  float lr, beta1, beta2, eps, wd, c1, c2_sqrt;  // c1 = 1 - beta1^t, c2_sqrt = sqrt(1 - beta2^t)
-  // phase profile (MXAR study knob, XgmiComm::set_phase_stamps): per (rank y, workgroup x)
-  // kPhaseSlots s_memrealtime values - see PhaseStamps below
-  uint64_t* stamps;
-  uint64_t delay;      // test knob: ticks rank `delay_rank` idles before phase 1
-  int delay_rank;
-  // test knob (XgmiComm::set_read_delay): ticks rank `rdelay_rank` idles before the phase that
-  // reads what peers pushed - holds a slow reader inside its launch (slot-reuse tests)
-  uint64_t rdelay;
-  int rdelay_rank;
-  // test knob (XgmiComm::set_forward_delay): ticks rank `fdelay_rank` idles before the ring's
-  // LAST all-gather forward (its late flag then races the next kernel's flags - the flag
-  // ownership test, tests/test_comm_gpu.py)
-  uint64_t fdelay;
-  int fdelay_rank;
-  int noguard;  // MXAR_SLOT_GUARD=0: skip entry_guard (A/B of its cost and negative control only)
-  int ring_hop_rows;  // study only (MXAR_RING_FLAGS=hop): the pre-fix ring flag layout, row = hop index
-  // threshold kernel with sub > 1 (chunks split into `sub` slices of `subchunk` elements,
-  // one workgroup each): the rank's own scratch, zeroed when the membership is configured.
-  // split_dec: 64-bit decision words, [c] own reduce chunk c, [maxch + j * maxch + c] gather
-  // unit (j, c); split_ctr: slice counters, [c] reduce, [maxch + j * maxch + c] scatter;
-  // split_early: [j * maxch + c] = epoch when gather unit (j, c) was in at launch
-  int sgroup;  // threshold kernel, unsplit chunks: chunks per scatter unit (one copy, one release)
-  // threshold kernel: the lag gate of round e may be taken as open when this rank's round e - 1
-  // was clean (it gathered every peer's reduced chunk of e - 1, so every peer had finished
-  // e - 2). Set by the host when that proof holds: trows >= 2 and every rank's block holds at
-  // least one chunk or the thresholds are full (XgmiComm::threshold_args).
-  int gate_shortcut;
-  // threshold kernel, protocol rounds with thresholds that tolerate a missing peer (unsplit
-  // chunks only): a peer still inside the round that last used this round's row after
-  // `lag_wait` ticks at the lag gate is SKIPPED for the round - nothing is written into its
-  // slab (its FORCE request still is), so a straggler never holds the fast ranks back. The
-  // laggard's late writes land in its own slots of our slab under older epochs, which no
-  // round of ours takes (xgmi_threshold.hip, lag gate). 0 = wait (the bounded-buffer gate).
-  int lag_skip;
-  uint64_t lag_wait;
-  // threshold kernel, full thresholds: the one-shot body (xgmi_threshold.hip) - every rank
-  // pushes its whole input as low-latency units and reduces every chunk itself (small rounds)
-  int oneshot;
-  uint64_t* split_dec;
-  uint32_t* split_ctr;
-  uint32_t* split_early;
-};
-
-// A plane group's resident kernel (threshold_group_resident_kernel): y = 0 is the dispatcher
-// row, y = 1 + k worker k's slice.
-struct GroupResArgs {
-  GroupResidentMember m[kMaxRanks];
-  uint32_t* gstate;  // pinned: [0] kResRunning / kResExiting / kResExited (the group's kernel)
-  uint64_t* gdm;     // device: [0] the dispatcher's heartbeat (100 MHz ticks)
-  uint64_t idle;     // ticks without a round before the kernel leaves
-  uint32_t gen;      // launch generation (the go words of a relaunched kernel differ)
-  int Y;             // workers
-};
-static_assert(sizeof(CommArgs) + sizeof(GroupResArgs) <= 4096, "threshold_group_resident_kernel arguments exceed 4 KiB");
 
 // Phase stamps of one workgroup (100 MHz s_memrealtime ticks): [0] start, [1] scatter done,
 // [2] ticks spent waiting in the reduce phase, [3] reduce phase done, [4] ticks spent
@@ -473,22 +366,5 @@ __device__ __forceinline__ void finish_launch_done(const CommArgs& a, uint32_t* 
     __hip_atomic_store(&ctl[0], epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
-
-
-// Host entry of the threshold kernel (xgmi_threshold.hip).
-void launch_threshold(const CommArgs& a, dim3 grid, hipStream_t s, DType dt);
-// A plane group's resident kernel: dim3(grid, workers + 1) (xgmi_threshold.hip).
-void launch_threshold_group_resident(const CommArgs& a, const GroupResArgs& g, int grid, hipStream_t s, DType dt);
-// Resident rounds (xgmi_threshold.hip; XgmiComm::launch_resident).
-void launch_threshold_resident(const CommArgs& a, int grid, hipStream_t s, DType dt, const ResidentDoor* door,
-                               uint32_t* hstate, uint32_t* dm, uint32_t seq, uint32_t gen, uint64_t idle_ticks);
-// Progress words = value in every peer's slab (xgmi_threshold.hip; XgmiComm::publish_progress).
-void launch_publish_progress(const CommArgs& a, uint32_t value, hipStream_t s);
-// Host entry of the low-latency one-shot (xgmi_ll.hip).
-void launch_ll(const CommArgs& a, dim3 grid, hipStream_t s, DType dt);
-// Host entry of the fused reduce-scatter + AdamW + all-gather (xgmi_adam.hip).
-void launch_adamw(const CommArgs& a, dim3 grid, hipStream_t s, DType dt);
-// Host entry of all-to-all (mode 0) / all-gather (1) / reduce-scatter (2) (xgmi_coll.hip).
-void launch_coll(const CommArgs& a, dim3 grid, hipStream_t s, DType dt, int mode);
 
 }  // namespace mxar

@@ -1941,48 +1941,44 @@ __global__ __launch_bounds__(64) void publish_progress_kernel(CommArgs a, uint32
 static bool full_fast(const CommArgs& a) { return a.full != 0 && a.sub <= 1; }
 static bool full_oneshot(const CommArgs& a) { return full_fast(a) && a.oneshot != 0; }
 
+// f(E{}, FULL, ONESHOT): the element type and the kernel variant of a round, as compile-time tags
+template <class Fn>
+static void dispatch_round(const CommArgs& a, DType dt, Fn&& f) {
+  dispatch_dtype(static_cast<int>(dt), [&](auto tag) {
+    if (full_oneshot(a))
+      f(tag, std::true_type{}, std::true_type{});
+    else if (full_fast(a))
+      f(tag, std::true_type{}, std::false_type{});
+    else
+      f(tag, std::false_type{}, std::false_type{});
+  });
+}
+
 void launch_publish_progress(const CommArgs& a, uint32_t value, hipStream_t s) {
   hipLaunchKernelGGL(publish_progress_kernel, dim3(1), dim3(64), 0, s, a, value);
 }
 
 void launch_threshold_resident(const CommArgs& a, int grid, hipStream_t s, DType dt, const ResidentDoor* door,
                                uint32_t* hstate, uint32_t* dm, uint32_t seq, uint32_t gen, uint64_t idle_ticks) {
-  dispatch_dtype(static_cast<int>(dt), [&](auto tag) {
-    using E = decltype(tag);
-    if (full_oneshot(a))
-      hipLaunchKernelGGL((threshold_resident_kernel<E, true, true>), dim3(grid), dim3(kCommThreads), 0, s, a, door,
-                         hstate, reinterpret_cast<uint64_t*>(dm), seq, gen, idle_ticks);
-    else if (full_fast(a))
-      hipLaunchKernelGGL((threshold_resident_kernel<E, true, false>), dim3(grid), dim3(kCommThreads), 0, s, a, door,
-                         hstate, reinterpret_cast<uint64_t*>(dm), seq, gen, idle_ticks);
-    else
-      hipLaunchKernelGGL((threshold_resident_kernel<E, false, false>), dim3(grid), dim3(kCommThreads), 0, s, a, door,
-                         hstate, reinterpret_cast<uint64_t*>(dm), seq, gen, idle_ticks);
+  dispatch_round(a, dt, [&](auto e, auto full, auto oneshot) {
+    constexpr bool FULL = decltype(full)::value, ONESHOT = decltype(oneshot)::value;
+    hipLaunchKernelGGL((threshold_resident_kernel<decltype(e), FULL, ONESHOT>), dim3(grid), dim3(kCommThreads), 0, s, a,
+                       door, hstate, reinterpret_cast<uint64_t*>(dm), seq, gen, idle_ticks);
   });
 }
 
 void launch_threshold(const CommArgs& a, dim3 grid, hipStream_t s, DType dt) {
-  dispatch_dtype(static_cast<int>(dt), [&](auto tag) {
-    using E = decltype(tag);
-    if (full_oneshot(a))
-      hipLaunchKernelGGL((threshold_kernel<E, true, true>), grid, dim3(kCommThreads), 0, s, a);
-    else if (full_fast(a))
-      hipLaunchKernelGGL((threshold_kernel<E, true, false>), grid, dim3(kCommThreads), 0, s, a);
-    else
-      hipLaunchKernelGGL((threshold_kernel<E, false, false>), grid, dim3(kCommThreads), 0, s, a);
+  dispatch_round(a, dt, [&](auto e, auto full, auto oneshot) {
+    constexpr bool FULL = decltype(full)::value, ONESHOT = decltype(oneshot)::value;
+    hipLaunchKernelGGL((threshold_kernel<decltype(e), FULL, ONESHOT>), grid, dim3(kCommThreads), 0, s, a);
   });
 }
 
 void launch_threshold_group_resident(const CommArgs& a, const GroupResArgs& g, int grid, hipStream_t s, DType dt) {
   const dim3 gd(static_cast<unsigned>(grid), static_cast<unsigned>(g.Y + 1));
-  dispatch_dtype(static_cast<int>(dt), [&](auto tag) {
-    using E = decltype(tag);
-    if (full_oneshot(a))
-      hipLaunchKernelGGL((threshold_group_resident_kernel<E, true, true>), gd, dim3(kCommThreads), 0, s, a, g);
-    else if (full_fast(a))
-      hipLaunchKernelGGL((threshold_group_resident_kernel<E, true, false>), gd, dim3(kCommThreads), 0, s, a, g);
-    else
-      hipLaunchKernelGGL((threshold_group_resident_kernel<E, false, false>), gd, dim3(kCommThreads), 0, s, a, g);
+  dispatch_round(a, dt, [&](auto e, auto full, auto oneshot) {
+    constexpr bool FULL = decltype(full)::value, ONESHOT = decltype(oneshot)::value;
+    hipLaunchKernelGGL((threshold_group_resident_kernel<decltype(e), FULL, ONESHOT>), gd, dim3(kCommThreads), 0, s, a, g);
   });
 }
 

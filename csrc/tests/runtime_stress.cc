@@ -26,6 +26,7 @@
 #include "../runtime/akka_endpoint.h"
 #include "../runtime/control_bridge.h"
 #include "../runtime/fault_injector.h"
+#include "../runtime/launch_geometry.h"
 #include "../runtime/loopback_plane.h"
 #include "../runtime/plane_worker.h"
 
@@ -554,11 +555,120 @@ static int run_akka(int P, int N, int C, int rounds) {
   return 0;
 }
 
+// The launch planner (launch_geometry.cc) over pseudo-random shapes: what the kernels rely on
+// holds for every geometry that does not throw (and the arithmetic never overflows: UBSan).
+static int run_geometry(int iters) {
+  uint64_t state = 0x9E3779B97F4A7C15ull;
+  auto rnd = [&state](uint64_t lo, uint64_t hi) {  // xorshift64*, fixed seed
+    state ^= state >> 12;
+    state ^= state << 25;
+    state ^= state >> 27;
+    return lo + (state * 0x2545F4914F6CDD1Dull >> 11) % (hi - lo + 1);
+  };
+  int failures = 0, planned = 0;
+  auto check = [&](bool ok, const char* what, const char* kind, const GridKnobs& k, int64_t n, int64_t es, int rh) {
+    if (ok) return;
+    if (failures++ < 10)
+      std::fprintf(stderr, "geometry: %s violated (%s world %d grid %d/%d n %lld es %lld ranks_here %d)\n", what, kind,
+                   k.world, k.grid, k.default_grid, static_cast<long long>(n), static_cast<long long>(es), rh);
+  };
+  for (int i = 0; i < iters; ++i) {
+    GridKnobs k;
+    k.world = static_cast<int>(rnd(1, kMaxRanks));
+    k.rows = static_cast<int>(rnd(1, 4));
+    k.default_grid = rnd(0, 3) ? 512 : static_cast<int>(rnd(1, 1024));
+    k.grid = rnd(0, 1) ? k.default_grid : static_cast<int>(rnd(1, 1024));
+    k.size_grid = rnd(0, 3) != 0;
+    const int64_t es = rnd(0, 1) ? 2 : 4;
+    const SlabLayout L = slab_layout(k.world, int64_t{1} << rnd(16, 28), k.rows - 1, 0, rnd(0, 3) ? 0 : 64, 512 * 1024);
+    k.maxch = L.maxch;
+    k.slot_bytes = L.slot_bytes;
+    k.geom = rnd(0, 1) ? -1 : static_cast<int>(rnd(0, 2));
+    k.units_per_wg = rnd(0, 3) ? 0 : static_cast<int>(rnd(1, 8));
+    k.sub_max = rnd(0, 3) ? 0 : static_cast<int>(rnd(1, 8));
+    k.ring_depth = static_cast<int>(rnd(1, 4));
+    k.ring_grid = rnd(0, 1) ? 256 : static_cast<int>(rnd(1, 1024));
+    k.th_oneshot_max = rnd(0, 3) ? 256 << 10 : 0;
+    const int rh = rnd(0, 1) ? 1 : k.world;
+    const int64_t n = static_cast<int64_t>(rnd(1, uint64_t{1} << rnd(1, 31)));
+    const int gcap = std::max(1, k.grid / rh);
+    auto common = [&](const LaunchGeometry& g, const char* kind, bool rounded, int gx_cap) {
+      ++planned;
+      check(g.gx >= 1 && g.gx <= gx_cap, "1 <= gx <= grid / ranks_here", kind, k, n, es, rh);
+      check(!rounded || (g.chunk * es) % 16 == 0, "chunk a multiple of 16 B", kind, k, n, es, rh);
+      check(static_cast<int64_t>(g.nch) * g.chunk >= g.block, "nch * chunk >= block", kind, k, n, es, rh);
+      check(static_cast<int64_t>(g.nch) * g.sub <= k.maxch, "nch * sub <= maxch", kind, k, n, es, rh);
+      check(g.block * es <= k.slot_bytes + 16, "block fits the slot", kind, k, n, es, rh);
+      check(g.sub >= 1 && static_cast<int64_t>(g.sub) * g.subchunk >= g.chunk, "sub * subchunk >= chunk", kind, k, n,
+            es, rh);
+    };
+    static const Algo algos[] = {Algo::OneShot, Algo::TwoShot, Algo::Ring, Algo::RingNative};
+    static const char* names[] = {"oneshot", "twoshot", "ring", "ring_native"};
+    for (int a = 0; a < 4; ++a) {
+      try {
+        common(plan_allreduce(algos[a], k, n, es, rh), names[a], true, gcap);
+      } catch (const std::logic_error&) {  // does not fit the slab: the caller segments
+      }
+    }
+    try {
+      common(plan_allreduce(Algo::TwoShot, k, n, es, rh, true), "adamw", true, gcap);
+    } catch (const std::logic_error&) {
+    }
+    if (n * es <= L.ll_max) {  // the low-latency kernel takes no flags and no S slots
+      const LaunchGeometry g = plan_ll(k, n, es, rh);
+      ++planned;
+      check(g.gx >= 1 && g.gx <= gcap && g.nch == 1 && g.block == n, "ll geometry", "ll", k, n, es, rh);
+    }
+    const int64_t m = std::min<int64_t>(std::max<int64_t>(16 / es, n / (16 / es) * (16 / es)), k.slot_bytes / es);
+    for (int op = 0; op < 3 && k.world > 1; ++op) {
+      try {
+        LaunchGeometry g = plan_coll(static_cast<Coll>(op), k, m, es, rh);
+        g.block = m;
+        common(g, "coll", true, gcap);
+      } catch (const std::logic_error&) {
+      }
+    }
+    static const float ths[] = {1.f, 0.9f, 0.75f, 0.5f};
+    const float thr = ths[rnd(0, 3)], thc = ths[rnd(0, 3)];
+    RoundShape spec;
+    if (rnd(0, 1) && rh == 1) {
+      spec.block = (n + k.world - 1) / k.world;
+      spec.chunk = static_cast<int64_t>(rnd(1, uint64_t{1} << rnd(1, 22)));
+      spec.order_ref = rnd(0, 1);
+      spec.split = rnd(0, 1);
+      spec.lag_skip = rnd(0, 1);
+    }
+    try {
+      const ThresholdPlan p = plan_threshold(k, n, es, rh, thr, thc, spec);
+      // the one-shot body of a shared launch is sized against the shared-launch cap alone, which
+      // an explicit grid lifts (the open one-shot item: plan_threshold's `cap`)
+      common(p, "threshold", spec.block == 0, p.oneshot && rh > 1 ? std::max(1, shared_launch_cap(k, rh)) : gcap);
+      const int64_t units = static_cast<int64_t>(std::max(1, k.world - 1)) * p.nch * p.sub;
+      check((units + p.gx - 1) / p.gx <= kThresholdGatherUnits || k.world == 1, "gather units per workgroup",
+            "threshold", k, n, es, rh);
+      check(p.min_reduce >= 1 && p.min_reduce <= k.world && p.min_complete >= 0 &&
+                p.min_complete <= static_cast<int64_t>(k.world) * p.nch,
+            "thresholds within the round", "threshold", k, n, es, rh);
+      check(!p.oneshot || (p.full && p.sub == 1 && k.world <= kOneshotRanks), "one-shot body only where it applies",
+            "threshold", k, n, es, rh);
+      check(!p.lag_skip || (spec.lag_skip && !p.split && p.min_reduce < k.world), "lag skip only where it is safe",
+            "threshold", k, n, es, rh);
+    } catch (const std::invalid_argument&) {  // does not fit one launch
+    }
+  }
+  if (failures != 0 || planned < iters) {
+    std::fprintf(stderr, "geometry: %d violations, %d geometries planned\n", failures, planned);
+    return 1;
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
   Logger::get().set_level(LogLevel::ERROR);
   const std::string only = argc > 1 ? argv[1] : "";
   int rc = 0;
-  if (only.empty() || only == "mailbox") rc = run_mailbox(6, 20000);
+  if (only.empty() || only == "geometry") rc = run_geometry(4000);
+  if (rc == 0 && (only.empty() || only == "mailbox")) rc = run_mailbox(6, 20000);
   if (rc == 0 && (only.empty() || only == "local")) rc = run_local(4, 37, 3, 30);
   if (rc == 0 && (only.empty() || only == "local2")) rc = run_local(3, 9, 2, 30);
   if (rc == 0 && (only.empty() || only == "tcp")) rc = run_tcp(20);

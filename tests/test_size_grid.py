@@ -1,4 +1,4 @@
-"""The launch-size grid rule (csrc/hip/xgmi_comm.h size_grid_rule, XgmiComm::launch_grid) on
+"""The launch-size grid rule (csrc/runtime/launch_geometry.h size_grid_rule, launch_grid) on
 the CPU: the workgroup counts the measured table in profiles/round4/README.md section 9 asks
 for (grid sweep: 8 logical ranks x 1 MiB best at 128, x 4 MiB / 16 MiB at 256, 256 MiB at the
 full grid; one-shot over P x bytes)."""
