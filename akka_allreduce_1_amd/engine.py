@@ -78,7 +78,7 @@ def host_iota_source(n: int, offset: float = 0.0) -> Callable:
 class PlaneJob:
     """Master + P plane workers in one process (threaded actor system).
 
-    Workers sharing a GPU form a plane group (csrc/hip/xgmi_plane.cc PlaneGroup): ONE
+    Workers sharing a GPU form a plane group (csrc/hip/plane_group.cc PlaneGroup): ONE
     resident kernel runs every round of every one of them, a slice of workgroups per worker
     fed from that worker's own door ring (xgmi_threshold.hip
     threshold_group_resident_kernel). Each worker's rounds still run on their own schedule (a

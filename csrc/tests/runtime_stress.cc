@@ -28,6 +28,7 @@
 #include "../runtime/fault_injector.h"
 #include "../runtime/launch_geometry.h"
 #include "../runtime/loopback_plane.h"
+#include "../runtime/plane_rounds.h"
 #include "../runtime/plane_worker.h"
 
 using namespace mxar;
@@ -663,11 +664,120 @@ static int run_geometry(int iters) {
   return 0;
 }
 
+// The round plane's host bookkeeping (plane_rounds.h): the slot ring and the lock-free hand-off
+// between a launching and a completion thread, and the decoding of a finished slot.
+static int run_rounds(int records) {
+  struct R {
+    int seq = 0, slot = 0;
+  };
+  constexpr int kRing = 4;
+  int failures = 0;
+  auto check = [&](bool ok, const char* what) {
+    if (!ok && failures++ < 10) std::fprintf(stderr, "rounds: %s\n", what);
+  };
+  {
+    RoundQueue<R> q;
+    q.reset_slots(kRing);
+    { auto dropped = q.take_slot(); }  // a lease dropped without commit returns its slot
+    if (q.free_slots() != kRing) {
+      std::fprintf(stderr, "rounds: a dropped lease kept its slot\n");
+      return 1;
+    }
+    std::atomic<int> in_flight{0}, max_in_flight{0}, consumed{0};
+    std::atomic<int> holder[kRing];
+    for (auto& h : holder) h.store(-1);
+    std::atomic<bool> fifo{true}, single{true}, ended{false};
+    std::thread consumer([&] {
+      R r;
+      for (int want = 0; q.wait_front(50, &r); ++want) {
+        if (r.seq != want) fifo.store(false);
+        if (holder[r.slot].exchange(-1) != r.seq) single.store(false);  // the slot was this record's alone
+        in_flight.fetch_sub(1);
+        consumed.fetch_add(1);
+        q.pop_and_release(r.slot);
+      }
+      ended.store(true);
+    });
+    uint64_t state = 0x9E3779B97F4A7C15ull;
+    for (int i = 0; i < records; ++i) {
+      if (i % 64 == 0) {  // the consumer both polls (short pauses) and sleeps (past its 50 us budget)
+        state = state * 6364136223846793005ull + 1442695040888963407ull;
+        std::this_thread::sleep_for(std::chrono::microseconds((state >> 33) % 201));
+      }
+      if (i % 97 == 0) {  // and so it does under load
+        auto dropped = q.take_slot();
+        check(holder[dropped.slot()].load() == -1, "a dropped lease's slot was held by a record");
+      }
+      auto lease = q.take_slot();
+      R r;
+      r.seq = i;
+      r.slot = lease.slot();
+      if (holder[r.slot].exchange(i) != -1) single.store(false);
+      const int now = in_flight.fetch_add(1) + 1;
+      for (int m = max_in_flight.load(); now > m && !max_in_flight.compare_exchange_weak(m, now);) {
+      }
+      lease.commit();
+      q.push(r);
+    }
+    q.drain();
+    check(consumed.load() == records && q.size() == 0, "drain() returned before the queue was empty");
+    check(fifo.load(), "records left the queue out of order");
+    check(single.load(), "a slot was held by two records at once");
+    check(max_in_flight.load() <= kRing && max_in_flight.load() >= 1, "more records in flight than ring slots");
+    check(q.free_slots() == kRing, "a slot was not returned");
+    std::this_thread::sleep_for(std::chrono::milliseconds(2));  // past its spin budget: the consumer sleeps
+    check(!ended.load(), "the consumer ended before stop()");
+    q.stop();
+    consumer.join();
+    check(ended.load(), "stop() did not end the consumer");
+  }
+  {
+    auto word = [](uint32_t epoch, uint32_t v) { return static_cast<int32_t>((epoch & 0xffffffu) << 8 | v); };
+    const uint32_t ep = 0x01000007u;  // the tag is the epoch's low 24 bits
+    auto ready = [&](const std::vector<int32_t>& w, size_t counts) {
+      size_t from = 0;
+      return slot_ready(w.data(), w.size(), counts, ep, &from);
+    };
+    {  // every tag present, coarse = 1; counts of 0 and of P
+      const int P = 3, nch = 2;
+      const size_t stride = P * nch + 4;
+      std::vector<int32_t> w(stride, 0);
+      const int cnt[] = {0, 3, 1, 2, 3, 0};
+      for (int i = 0; i < P * nch; ++i) w[i] = word(ep, cnt[i]);
+      w[stride - 1] = word(ep, 0x12);
+      const SlotResult r = decode_slot(w.data(), stride, P, nch, nch, 1);
+      check(ready(w, P * nch) && r.error == 0x12u && r.count == std::vector<int32_t>(cnt, cnt + 6), "decode_slot: plain slot");
+      w[2] = word(ep - 1, 1);  // one count still carries the previous epoch's tag
+      check(!ready(w, P * nch), "slot_ready: stale count taken as ready");
+      w[2] = word(ep, 1);
+      w[stride - 1] = 0x12;  // the error word's tag is missing
+      check(!ready(w, P * nch), "slot_ready: untagged error word taken as ready");
+      size_t from = 0;
+      check(!slot_ready(w.data(), stride, P * nch, ep, &from) && from == static_cast<size_t>(P * nch),
+            "slot_ready: counts not advanced past their tags");
+    }
+    {  // coarsened: count[j * 5 + c] = cnt[j * 2 + c / 3]
+      const int P = 2, nch = 2, nch_ref = 5, coarse = 3;
+      const size_t stride = P * nch + 4;
+      std::vector<int32_t> w(stride, 0);
+      const int cnt[] = {2, 1, 0, 2};
+      for (int i = 0; i < P * nch; ++i) w[i] = word(ep, cnt[i]);
+      w[stride - 1] = word(ep, 0);
+      const SlotResult r = decode_slot(w.data(), stride, P, nch, nch_ref, coarse);
+      check(ready(w, P * nch) && r.error == 0 && r.count == std::vector<int32_t>({2, 2, 2, 1, 1, 0, 0, 0, 2, 2}),
+            "decode_slot: coarsened expansion");
+    }
+  }
+  if (failures != 0) std::fprintf(stderr, "rounds: %d checks failed\n", failures);
+  return failures != 0;
+}
+
 int main(int argc, char** argv) {
   Logger::get().set_level(LogLevel::ERROR);
   const std::string only = argc > 1 ? argv[1] : "";
   int rc = 0;
   if (only.empty() || only == "geometry") rc = run_geometry(4000);
+  if (rc == 0 && (only.empty() || only == "rounds")) rc = run_rounds(5000);
   if (rc == 0 && (only.empty() || only == "mailbox")) rc = run_mailbox(6, 20000);
   if (rc == 0 && (only.empty() || only == "local")) rc = run_local(4, 37, 3, 30);
   if (rc == 0 && (only.empty() || only == "local2")) rc = run_local(3, 9, 2, 30);

@@ -925,6 +925,73 @@ def test_one_worker_per_process_resident_and_launched_rounds(resident):
                 assert res_rounds == 0, (rank, n, out)
 
 
+def _solo_kinds_worker(rank, world, port, q):
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
+    import torch.distributed as dist
+
+    from akka_allreduce_1_amd.engine import distributed_plane_job
+
+    torch.cuda.set_device(0)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    out = []
+    try:
+        rounds = 6
+        for resident in (True, False):  # the plane's constructor reads it: switched between jobs
+            if resident:
+                os.environ.pop("MXAR_PLANE_RESIDENT", None)
+            else:
+                os.environ["MXAR_PLANE_RESIDENT"] = "0"
+            # both cast directions: a float32 plane at one shape, a bfloat16 plane at the other
+            for n, chunk, dtype in ((10, 2, torch.float32), (1031, 129, torch.bfloat16)):
+                mine = _kind_values(n, rank)
+                host = mine.numpy()
+                want = sum(_kind_values(n, k) for k in range(world)).to(dtype)
+                for kind, src in (("host", lambda req: host), ("same", mine.to(dtype).to(DEV)),
+                                  ("other", mine.to(_other(dtype)).to(DEV))):
+                    res = distributed_plane_job(n, src, max_chunk_size=chunk, dtype=dtype, rounds=rounds, grid=64,
+                                                keep_last=True, timeout_s=60.0)
+                    y = res["last"]
+                    ok = bool(res["ok"] and y is not None and y.iteration == rounds - 1
+                              and y.data.dtype == dtype and torch.equal(y.data.cpu(), want))
+                    out.append((resident, n, kind, ok, res["plane"]["launches"], res["plane"]["resident_rounds"]))
+    except Exception as e:  # report, never hang the parent
+        out.append(("error", repr(e)))
+    q.put((rank, out))
+    dist.destroy_process_group()
+
+
+def test_solo_rounds_take_every_input_kind():
+    """One plane worker per process (2 processes on one GPU), residency on and then off, both
+    shapes of test_group_rounds_take_every_input_kind, one job of 6 rounds per input kind: a
+    host payload, a device tensor of the plane dtype, a device tensor of the other dtype. The
+    last output is the exact sum (no tolerance) and every round was submitted once; a host
+    payload, an input of another dtype and every round with residency off take the launch path."""
+    import multiprocessing as mp
+
+    from akka_allreduce_1_amd.parallel import free_port
+
+    world = 2
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = free_port()
+    procs = [ctx.Process(target=_solo_kinds_worker, args=(r, world, port, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    res = [q.get(timeout=240) for _ in range(world)]
+    for p in procs:
+        p.join(timeout=60)
+        if p.is_alive():
+            p.kill()
+    for rank, out in res:
+        print(rank, out)
+        assert not any(o[0] == "error" for o in out), (rank, out)
+        assert len(out) == 12, (rank, out)
+        for resident, n, kind, ok, launches, res_rounds in out:
+            assert ok and launches == 6, (rank, resident, n, kind, out)
+            if not resident or kind != "same":
+                assert res_rounds == 0, (rank, resident, n, kind, out)
+
+
 # ---------------------------------------------------------------------------------------
 # Co-located workers (xgmi_plane.cc PlaneGroup, xgmi_threshold.hip
 # threshold_group_resident_kernel): the workers of a job in one process on one GPU run every
@@ -964,6 +1031,48 @@ def test_group_rounds_exact(P, n, chunk, dtype):
                     np.testing.assert_array_equal(data.cpu().numpy(), expected(n, it, range(P)))
                 else:
                     assert _bf16_close(data, n, it, P), (k, it)
+    finally:
+        job.shutdown()
+
+
+def _kind_values(n, k):
+    """Worker k's input of the input-kind tests: (i % 61) + k, float32. With three workers every
+    sum stays below 256: exact in bf16 and in fp32."""
+    return (torch.arange(n, dtype=torch.float32) % 61) + float(k)
+
+
+def _other(dtype):
+    return torch.bfloat16 if dtype == torch.float32 else torch.float32
+
+
+@pytest.mark.parametrize("n,chunk", [(10, 2), (1031, 129)])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_group_rounds_take_every_input_kind(dtype, n, chunk):
+    """Co-located workers, one input kind each: worker 0 a host payload (a callable returning a
+    NumPy float32 array: staged on the side stream), worker 1 a device tensor of the plane
+    dtype (used directly), worker 2 a device tensor of the other dtype (cast on the side
+    stream). n = 10 / chunk 2 is the reference's default job (one workgroup); n = 1031 / chunk
+    129 has an uneven last block, an uneven last chunk and element offsets off 16 bytes. Every
+    round of every worker is the exact sum in the plane dtype (no tolerance), every count 3."""
+    P, rounds = 3, 6
+    host = _kind_values(n, 0).numpy()
+    sources = [lambda req: host, _kind_values(n, 1).to(dtype).to(DEV), _kind_values(n, 2).to(_other(dtype)).to(DEV)]
+    want = sum(_kind_values(n, k) for k in range(P)).to(dtype)
+    job = PlaneJob(P, n, max_chunk_size=chunk, max_lag=1, max_round=rounds - 1, dtype=dtype, sources=sources,
+                   timeout_s=20.0)
+    try:
+        job.run(timeout=120)
+        assert job.rounds["n"] == rounds
+        for k in range(P):
+            st = job.system.plane_worker_state(job.workers[k])
+            assert st["stats"]["plane_errors"] == 0, st
+            s = job.planes[k].stats
+            assert s.group_rounds == rounds and s.launches == rounds, (k, s.group_rounds, s.launches)
+            for it in range(rounds):
+                data, counts = job.outputs[k][it]
+                assert data.dtype == dtype
+                assert torch.equal(data.cpu(), want), (k, it)
+                assert list(counts) == [P] * len(counts), (k, it, counts)
     finally:
         job.shutdown()
 

@@ -19,6 +19,9 @@ experiments (every cell validated against an fp32 sum before it is timed):
   sdma-remap the copy-engine allreduce before / after its input (x), output (y) or both
              were freed, the cache emptied and re-allocated at the same addresses, and with
              the input staged through a buffer allocated first (--mode x|y|both)
+  plane-paths  one round path of the round plane (--case group: in-process 40 B PlaneJob rounds on
+             the group kernel; --case solo: mxar master + 2 mxar-gpu workers at 256 KiB, resident
+             rounds, or launched ones with --env MXAR_PLANE_RESIDENT=0), us per round
   grid       protocol rounds (2 workers, th = 1) at several per-worker workgroup budgets
   coll-grid  all-gather / reduce-scatter / all-to-all over device workgroup budgets
 
@@ -108,6 +111,21 @@ def exp_protocol(a) -> None:
             row["native_us"] = {k: v.get("us_per_round") for k, v in nat.items() if isinstance(v, dict) and "us_per_round" in v}
             row["native_ok"] = all(v.get("validated") for v in nat.values() if isinstance(v, dict) and "validated" in v)
         _emit(row)
+
+
+def exp_plane_paths(a) -> None:
+    import torch
+
+    import akka_allreduce_1_amd
+    from benchmarks.sections import native_deployment, protocol_sizes
+
+    if a.case == "group":
+        r = protocol_sizes(torch.device("cuda", 0), cases=((40, torch.float32, 2, 2000),))["40B"]
+    else:
+        r = native_deployment(cases=((65536, 1024, 400),), budget_s=60.0)["262144B"]
+    _emit({"exp": "plane-paths", "case": a.case, "tag": a.tag, "resident": os.environ.get("MXAR_PLANE_RESIDENT"),
+           "pkg": os.path.basename(os.path.dirname(os.path.dirname(os.path.abspath(akka_allreduce_1_amd.__file__)))),
+           **{k: r.get(k) for k in ("us_per_round", "round_interval_p50_us", "round_interval_p99_us", "validated", "error")}})
 
 
 def exp_ring(a) -> None:
@@ -315,6 +333,8 @@ def main() -> None:
     p = sub.add_parser("protocol")
     p.add_argument("--reps", type=int, default=1)
     p.add_argument("--native", type=int, default=1)
+    p = sub.add_parser("plane-paths")
+    p.add_argument("--case", default="group", choices=["group", "solo"])
     p = sub.add_parser("ring")
     p.add_argument("--P", type=int, default=8)
     p.add_argument("--mib", type=int, default=256)
@@ -340,7 +360,7 @@ def main() -> None:
         s.add_argument("--tag", default="")
     a = ap.parse_args()
     _setup(a.env)
-    {"threshold": exp_threshold, "protocol": exp_protocol, "ring": exp_ring, "sdma": exp_sdma, "sdma-remap": exp_sdma_remap, "grid": exp_grid,
+    {"threshold": exp_threshold, "protocol": exp_protocol, "plane-paths": exp_plane_paths, "ring": exp_ring, "sdma": exp_sdma, "sdma-remap": exp_sdma_remap, "grid": exp_grid,
      "coll-grid": exp_coll_grid}[a.exp](a)
 
 

@@ -1,4 +1,4 @@
-"""Co-located plane workers on the group kernel (csrc/hip/xgmi_plane.cc PlaneGroup): run one
+"""Co-located plane workers on the group kernel (csrc/hip/plane_group.cc PlaneGroup): run one
 PlaneJob shape and, if it stalls, print every plane's door / group / control words
 (XgmiRoundPlane.debug_state) - the diagnosis of a stuck slice.
 
