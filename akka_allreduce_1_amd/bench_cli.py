@@ -11,6 +11,7 @@ algbw * 2(P-1)/P (nccl-tests convention). Engines:
   ll                        low-latency one-shot, flags inside the data (csrc/hip/xgmi_ll.hip)
   all_to_all / all_gather / reduce_scatter   xGMI collectives (csrc/hip/xgmi_coll.hip); SIZE =
                             the full [world x m] buffer (all_gather: its output)
+  broadcast / reduce        rooted xGMI collectives, root 0 (csrc/hip/xgmi_rooted.hip); SIZE = the tensor
   threshold                 straggler-tolerant kernel at th = 1 (csrc/hip/xgmi_threshold.hip)
   rccl                      torch.distributed all_reduce on the nccl (= RCCL) backend
   torch                     torch.distributed all_reduce on whatever backend (gloo on CPU)
@@ -112,6 +113,12 @@ def main(argv: list[str] | None = None) -> int:
 
                     def fn(algo=algo, ins=ins, outs=outs):
                         cl.collective(algo, ins, outs)
+                elif algo == "broadcast":
+                    def fn():
+                        cl.broadcast([y[:n] for y in ys], 0)
+                elif algo == "reduce":
+                    def fn():
+                        cl.reduce([x[:n] for x in xs], 0, ys[0][:n], scale=1.0 / P if args.op == "avg" else 1.0)
                 else:
                     def fn():
                         cl.allreduce([x[:n] for x in xs], [y[:n] for y in ys], algo=algo, op=args.op)
@@ -129,7 +136,7 @@ def main(argv: list[str] | None = None) -> int:
         on_gpu = args.backend == "nccl"
         dev = torch.device("cuda", local) if on_gpu else torch.device("cpu")
         comm = None
-        if on_gpu and any(a in ("ll", "oneshot", "twoshot", "ring", "threshold") + ("all_to_all", "all_gather", "reduce_scatter") for a in args.algos):
+        if on_gpu and any(a in ("ll", "oneshot", "twoshot", "ring", "threshold") + ("all_to_all", "all_gather", "reduce_scatter", "broadcast", "reduce") for a in args.algos):
             from .parallel import XgmiCommunicator
 
             comm = XgmiCommunicator(slot_bytes=max(64 << 20, -(-max(sizes) // P) + (1 << 20)),
@@ -161,6 +168,13 @@ def main(argv: list[str] | None = None) -> int:
                         fn = lambda m=m: comm.all_to_all(x[:P * m], y[:P * m])  # noqa: E731
                     else:
                         fn = lambda m=m: comm.reduce_scatter(x[:P * m], y[:m])  # noqa: E731
+                elif algo in ("broadcast", "reduce"):
+                    if comm is None:
+                        continue
+                    if algo == "broadcast":
+                        fn = lambda: comm.broadcast(y[:n], 0)  # noqa: E731
+                    else:
+                        fn = lambda: comm.reduce(x[:n], y[:n] if rank == 0 else None, 0, op=args.op)  # noqa: E731
                 elif algo in ("rccl", "torch"):
                     if algo == "rccl" and not on_gpu:
                         continue

@@ -490,6 +490,86 @@ class XgmiCommunicator:
                 out.div_(self.world)
         return out
 
+    # ------------------------------------------------------------------ rooted collectives
+    def _rooted_ok(self, t: torch.Tensor, root: int, what: str) -> bool:
+        if not 0 <= root < self.world:
+            raise ValueError(f"{what} must be a rank in [0, {self.world})")
+        if t.get_device() != self._dev:
+            raise ValueError(f"tensors must live on {self.device}")
+        if not t.is_contiguous():
+            raise ValueError("tensors must be contiguous")
+        return t.dtype in _KERNEL_DTYPES and t.data_ptr() % 16 == 0
+
+    def _global_rank(self, r: int) -> int:
+        import torch.distributed as dist
+
+        return r if self.group is None else dist.get_global_rank(self.group, r)
+
+    def _host_staged(self) -> bool:
+        """A gloo group (the single-GPU rehearsals) moves the fall-back tensors through the host."""
+        import torch.distributed as dist
+
+        return dist.get_backend(self.group) == "gloo"
+
+    def broadcast(self, t: torch.Tensor, src: int = 0, *, stream: int | None = None) -> torch.Tensor:
+        """t on every rank = t of rank `src`, in place (like torch.distributed.broadcast). One
+        xGMI launch per segment (csrc/hip/xgmi_rooted.hip): the root scatters its blocks and
+        the ranks all-gather them. torch.distributed for dtypes the kernels do not cover (the
+        int64 buffers of a module) and for tensors that are not 16-byte aligned."""
+        if self._rooted_ok(t, src, "src"):
+            self._c.broadcast(t.data_ptr(), t.numel(), _KERNEL_DTYPES[t.dtype], src,
+                              _current_stream(self._dev) if stream is None else stream)
+        else:
+            import torch.distributed as dist
+
+            with self._on_stream(stream):
+                buf = t.cpu() if self._host_staged() else t
+                dist.broadcast(buf, src=self._global_rank(src), group=self.group)
+                if buf is not t:
+                    t.copy_(buf)
+        return t
+
+    def reduce(self, inp: torch.Tensor, out: torch.Tensor | None = None, dst: int = 0, *, op: str = "sum",
+               stream: int | None = None) -> torch.Tensor | None:
+        """out on rank `dst` = sum (or mean) over ranks of inp: fp32 accumulation in rank order,
+        one rounding. Returns `out` on `dst` (allocated when not given) and None elsewhere,
+        where `out` is ignored. One xGMI launch per segment: a reduce-scatter whose owners
+        write their reduced block into the root's slab (csrc/hip/xgmi_rooted.hip)."""
+        if op != "sum" and op != "avg":
+            raise ValueError(f"unsupported op {op!r}")
+        kernel = self._rooted_ok(inp, dst, "dst")
+        root = self.rank == dst
+        if root:
+            if out is None:
+                out = torch.empty_like(inp)
+            if out.get_device() != self._dev or not out.is_contiguous() or out.numel() != inp.numel() \
+                    or out.dtype != inp.dtype:
+                raise ValueError("inp/out must be contiguous on the device with the same numel and dtype")
+        else:
+            out = None
+        if kernel:
+            # every rank takes the same path: dtype and alignment of `inp` decide; a misaligned
+            # `out` on the root is reduced into a copy
+            tmp = torch.empty_like(inp) if root and out.data_ptr() % 16 else None
+            target = tmp if tmp is not None else out
+            self._c.reduce(inp.data_ptr(), 0 if target is None else target.data_ptr(), inp.numel(),
+                           _KERNEL_DTYPES[inp.dtype], dst, _current_stream(self._dev) if stream is None else stream,
+                           1.0 / self.world if op == "avg" else 1.0)
+            if tmp is not None:
+                with self._on_stream(stream):
+                    out.copy_(tmp)
+        else:
+            import torch.distributed as dist
+
+            with self._on_stream(stream):
+                buf = inp.cpu() if self._host_staged() else inp.clone()
+                dist.reduce(buf, dst=self._global_rank(dst), group=self.group)
+                if root:
+                    out.copy_(buf)
+                    if op == "avg":
+                        out.div_(self.world)
+        return out
+
     def barrier(self) -> None:
         self._c.barrier(torch.cuda.current_stream(self.device).cuda_stream)
 
@@ -753,6 +833,46 @@ class LocalCluster:
                                          [outputs[k].data_ptr() for k in g], m, code,
                                          torch.cuda.current_stream(dev).cuda_stream, scale)
         return list(outputs)
+
+    def _check_rooted(self, tensors, root: int) -> None:
+        if len(tensors) != self.world:
+            raise ValueError("one tensor per logical rank")
+        if not 0 <= root < self.world:
+            raise ValueError(f"root must be a rank in [0, {self.world})")
+        n, dt = tensors[0].numel(), tensors[0].dtype
+        for k, t in enumerate(tensors):
+            if t.numel() != n or t.dtype != dt or not t.is_contiguous():
+                raise ValueError("all ranks must pass contiguous tensors of the same shape and dtype")
+            if t.device != self.devices[k]:
+                raise ValueError(f"rank {k} tensors must live on {self.devices[k]}")
+
+    def broadcast(self, tensors: Sequence[torch.Tensor], src: int = 0) -> list[torch.Tensor]:
+        """tensors[k] = tensors[src] for every logical rank, in place (xgmi_rooted.hip)."""
+        self._check_rooted(tensors, src)
+        code = _dtype_code(tensors[0].dtype)
+        for g in self.groups:
+            dev = self.devices[g[0]]
+            _H.XgmiComm.broadcast_local([self.comms[k] for k in g], [tensors[k].data_ptr() for k in g],
+                                        tensors[0].numel(), code, src, _current_stream(dev.index))
+        return list(tensors)
+
+    def reduce(self, inputs: Sequence[torch.Tensor], dst: int = 0, output: torch.Tensor | None = None, *,
+               scale: float = 1.0) -> torch.Tensor:
+        """output (on rank dst's device) = scale * sum over the logical ranks of inputs[k]: fp32
+        accumulation in rank order, one rounding (xgmi_rooted.hip). Returns it."""
+        self._check_rooted(inputs, dst)
+        if output is None:
+            output = torch.empty_like(inputs[dst])
+        if output.numel() != inputs[dst].numel() or output.dtype != inputs[dst].dtype \
+                or output.device != self.devices[dst] or not output.is_contiguous():
+            raise ValueError(f"output must match the inputs and live on {self.devices[dst]}")
+        code = _dtype_code(inputs[0].dtype)
+        for g in self.groups:
+            dev = self.devices[g[0]]
+            _H.XgmiComm.reduce_local([self.comms[k] for k in g], [inputs[k].data_ptr() for k in g],
+                                     [output.data_ptr() if k == dst else 0 for k in g], inputs[0].numel(), code, dst,
+                                     _current_stream(dev.index), scale)
+        return output
 
     def step_adamw(self, grads: Sequence[torch.Tensor], params: Sequence[torch.Tensor], states: Sequence[dict], *,
                    lr: float, betas: tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,

@@ -127,6 +127,77 @@ class TorchDistComm:
         dist.all_gather_into_tensor(out, inp, group=self.group)
         return out
 
+    def _global_rank(self, r: int) -> int:
+        import torch.distributed as dist
+
+        return r if self.group is None else dist.get_global_rank(self.group, r)
+
+    def broadcast(self, t: torch.Tensor, src: int = 0) -> torch.Tensor:
+        import torch.distributed as dist
+
+        if not 0 <= src < self.world:
+            raise ValueError(f"src must be a rank in [0, {self.world})")
+        dist.broadcast(t, src=self._global_rank(src), group=self.group)
+        return t
+
+    def reduce(self, inp: torch.Tensor, out: torch.Tensor | None = None, dst: int = 0, *,
+               op: str = "sum") -> torch.Tensor | None:
+        """Returns `out` on `dst` (allocated when not given) and None elsewhere."""
+        import torch.distributed as dist
+
+        if op not in ("sum", "avg"):
+            raise ValueError(f"unsupported op {op!r}")
+        if not 0 <= dst < self.world:
+            raise ValueError(f"dst must be a rank in [0, {self.world})")
+        buf = inp.clone()  # torch.distributed reduces in place and leaves partial sums off the root
+        dist.reduce(buf, dst=self._global_rank(dst), group=self.group)
+        if self.rank != dst:
+            return None
+        if out is None:
+            return buf.div_(self.world) if op == "avg" else buf
+        out.copy_(buf)
+        return out.div_(self.world) if op == "avg" else out
+
+
+def broadcast_parameters(module: torch.nn.Module, comm, src: int = 0, *, buffers: bool = True,
+                         bucket_bytes: int = 64 << 20) -> int:
+    """Make every rank's parameters (and buffers) those of rank `src`: the reducers below
+    assume replicas that start identical, and a checkpoint is usually loaded on one rank.
+    Tensors are flattened per dtype into buckets of ~`bucket_bytes`, each bucket is broadcast
+    with `comm.broadcast(tensor, src)` (XgmiCommunicator, TorchDistComm, ...) and copied back.
+    Call it once, before the reducer is built. Returns the number of tensors broadcast."""
+    tensors = [p.data for p in module.parameters()]
+    if buffers:
+        tensors += [b.data for b in module.buffers()]
+    seen, groups = set(), {}
+    for t in tensors:  # tied weights once; registration order is the same on every rank
+        if t.data_ptr() in seen and t.numel():
+            continue
+        seen.add(t.data_ptr())
+        groups.setdefault((t.dtype, t.device), []).append(t)
+    count = 0
+    for (dtype, device), ts in groups.items():
+        cap = max(1, bucket_bytes // torch.empty(0, dtype=dtype).element_size())
+        buckets, cur, cur_n = [], [], 0
+        for t in ts:
+            if cur and cur_n + t.numel() > cap:
+                buckets.append(cur)
+                cur, cur_n = [], 0
+            cur.append(t)
+            cur_n += t.numel()
+        if cur:
+            buckets.append(cur)
+        for bucket in buckets:
+            flat = torch.cat([t.reshape(-1) for t in bucket]) if len(bucket) > 1 else bucket[0].reshape(-1).clone()
+            if flat.numel():
+                comm.broadcast(flat, src)
+            off = 0
+            for t in bucket:
+                t.copy_(flat[off:off + t.numel()].view_as(t))
+                off += t.numel()
+            count += len(bucket)
+    return count
+
 
 @dataclass
 class GradBucket:

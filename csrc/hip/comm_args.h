@@ -150,6 +150,9 @@ struct CommArgs {
   // threshold kernel, full thresholds: the one-shot body (xgmi_threshold.hip) - every rank
   // pushes its whole input as low-latency units and reduces every chunk itself (small rounds)
   int oneshot;
+  // rooted collectives (xgmi_rooted.hip): the rank that holds the tensor (broadcast) or
+  // receives the sum (reduce); 0 for every other kernel
+  int root;
   uint64_t* split_dec;
   uint32_t* split_ctr;
   uint32_t* split_early;

@@ -310,6 +310,15 @@ void bind_hip(py::module_& m) {
       py::arg("op"), py::arg("knobs"), py::arg("n"), py::arg("elem_size"), py::arg("ranks_here") = 1,
       "geometry of one collective segment of n elements per block");
   h.def(
+      "plan_rooted",
+      [](const std::string& kind, const GridKnobs& k, int64_t n, int64_t es, int ranks_here) {
+        const int code = kind == "broadcast" ? 0 : kind == "reduce" ? 1 : -1;
+        if (code < 0) throw std::invalid_argument("plan_rooted: kind is broadcast or reduce");
+        return geometry_dict(plan_rooted(static_cast<Rooted>(code), k, n, es, ranks_here));
+      },
+      py::arg("kind"), py::arg("knobs"), py::arg("n"), py::arg("elem_size"), py::arg("ranks_here") = 1,
+      "geometry of one broadcast / reduce segment of n elements in all");
+  h.def(
       "plan_threshold",
       [](const GridKnobs& k, int64_t n, int64_t es, int ranks_here, float thr, float thc, int64_t block, int64_t chunk,
          bool order_ref, bool split, bool lag_skip) {
@@ -626,6 +635,45 @@ void bind_hip(py::module_& m) {
             XgmiComm::collective_local(comms, op, i, o, m, dt, as_stream(stream), scale);
           },
           py::arg("comms"), py::arg("op"), py::arg("inputs"), py::arg("outputs"), py::arg("m"), py::arg("dtype"),
+          py::arg("stream") = 0, py::arg("scale") = 1.0f)
+      .def(
+          "broadcast",
+          [](XgmiComm& c, uintptr_t buf, int64_t n, DType dt, int root, uintptr_t stream) {
+            py::gil_scoped_release r;
+            c.broadcast(as_ptr(buf), n, dt, root, as_stream(stream));
+          },
+          py::arg("buf"), py::arg("n"), py::arg("dtype"), py::arg("root") = 0, py::arg("stream") = 0)
+      .def(
+          "reduce",
+          [](XgmiComm& c, uintptr_t in, uintptr_t out, int64_t n, DType dt, int root, uintptr_t stream, float scale) {
+            py::gil_scoped_release r;
+            c.reduce(as_cptr(in), as_ptr(out), n, dt, root, as_stream(stream), scale);
+          },
+          py::arg("inp"), py::arg("out"), py::arg("n"), py::arg("dtype"), py::arg("root") = 0, py::arg("stream") = 0,
+          py::arg("scale") = 1.0f)
+      .def_static(
+          "broadcast_local",
+          [](const std::vector<XgmiComm*>& comms, const std::vector<uintptr_t>& bufs, int64_t n, DType dt, int root,
+             uintptr_t stream) {
+            std::vector<void*> b;
+            for (auto p : bufs) b.push_back(as_ptr(p));
+            py::gil_scoped_release r;
+            XgmiComm::broadcast_local(comms, b, n, dt, root, as_stream(stream));
+          },
+          py::arg("comms"), py::arg("bufs"), py::arg("n"), py::arg("dtype"), py::arg("root") = 0,
+          py::arg("stream") = 0)
+      .def_static(
+          "reduce_local",
+          [](const std::vector<XgmiComm*>& comms, const std::vector<uintptr_t>& ins, const std::vector<uintptr_t>& outs,
+             int64_t n, DType dt, int root, uintptr_t stream, float scale) {
+            std::vector<const void*> i;
+            std::vector<void*> o;
+            for (auto p : ins) i.push_back(as_cptr(p));
+            for (auto p : outs) o.push_back(as_ptr(p));
+            py::gil_scoped_release r;
+            XgmiComm::reduce_local(comms, i, o, n, dt, root, as_stream(stream), scale);
+          },
+          py::arg("comms"), py::arg("inputs"), py::arg("outputs"), py::arg("n"), py::arg("dtype"), py::arg("root") = 0,
           py::arg("stream") = 0, py::arg("scale") = 1.0f)
       .def_static(
           "barrier_local",

@@ -830,5 +830,91 @@ void XgmiComm::collective_local(const std::vector<XgmiComm*>& comms, Coll op, co
   run_coll(comms, op, ins, outs, m, dt, stream, scale);
 }
 
+void XgmiComm::run_rooted(const std::vector<XgmiComm*>& group, Rooted kind, const std::vector<const void*>& ins,
+                          const std::vector<void*>& outs_in, int64_t n, DType dt, int root, hipStream_t stream,
+                          float scale) {
+  const bool reduce = kind == Rooted::Reduce;
+  std::vector<void*> outs = outs_in;
+  if (reduce && !group.empty() && outs.size() == group.size())
+    for (size_t y = 0; y < group.size(); ++y)
+      if (group[y]->rank_ != root) outs[y] = nullptr;  // ignored off the root
+  check_group(group, ins, outs);
+  const XgmiComm& c0 = *group[0];
+  const int W = c0.world_;
+  if (root < 0 || root >= W) throw std::invalid_argument("XgmiComm: root must be in [0, world)");
+  const int64_t es = static_cast<int64_t>(dtype_size(dt));
+  if (reduce && n > 0)
+    for (size_t y = 0; y < group.size(); ++y) {
+      if (group[y]->rank_ != root) continue;
+      if (outs[y] == nullptr) throw std::invalid_argument("XgmiComm: reduce needs an output on the root");
+      const uintptr_t i0 = reinterpret_cast<uintptr_t>(ins[y]), o0 = reinterpret_cast<uintptr_t>(outs[y]);
+      if (i0 < o0 + static_cast<uintptr_t>(n * es) && o0 < i0 + static_cast<uintptr_t>(n * es))
+        throw std::invalid_argument("XgmiComm: reduce input and output must not overlap on the root");
+    }
+  if (n <= 0) return;
+  hip_check(hipSetDevice(c0.device_), "hipSetDevice");
+  for (XgmiComm* c : group) {
+    ++c->stats_.calls;
+    c->stats_.bytes += n * es;
+  }
+  order_group(group, stream);
+  if (W == 1) {  // one rank: nothing to send; a reduce is a copy (scaled)
+    for (size_t y = 0; reduce && y < group.size(); ++y) {
+      if (scale != 1.f)
+        launch_reduce_slots(ins[y], 0, 1, outs[y], n, dt, scale, stream);  // one slot: no stride (any n)
+      else
+        launch_copy(ins[y], outs[y], n * es, stream);
+    }
+    return;
+  }
+  TraceScope span("xgmi", [&] {
+    return std::make_pair(std::string(reduce ? "reduce " : "broadcast ") + std::to_string(n * es) + "B",
+                          "{\"rank\":" + std::to_string(c0.rank_) + ",\"root\":" + std::to_string(root) +
+                              ",\"ranks_in_launch\":" + std::to_string(group.size()) + "}");
+  });
+  const int ranks_here = static_cast<int>(group.size());
+  const GridKnobs knobs = c0.knobs();
+  const int64_t seg = W * (c0.slot_bytes_ / es);  // one block fits one slot, as the two-shot's segments
+  for (int64_t off = 0; off < n; off += seg) {
+    const int64_t len = std::min(seg, n - off);
+    const LaunchGeometry g = plan_rooted(kind, knobs, len, es, ranks_here);
+    CommArgs a = c0.base_args(group);
+    for (size_t y = 0; y < group.size(); ++y) {
+      a.in[y] = static_cast<const char*>(ins[y]) + off * es;
+      a.out[y] = outs[y] == nullptr ? nullptr : static_cast<char*>(outs[y]) + off * es;
+    }
+    set_geometry(a, g);
+    a.n = len;
+    a.scale = scale;
+    a.root = root;
+    launch_rooted(a, dim3(g.gx, ranks_here), stream, dt, kind);
+    hip_check(hipGetLastError(), "rooted collective launch");
+    for (XgmiComm* c : group) {
+      ++c->stats_.launches;
+      ++c->stats_.coll;
+    }
+  }
+}
+
+void XgmiComm::broadcast(void* buf, int64_t n, DType dt, int root, hipStream_t stream) {
+  run_rooted({this}, Rooted::Broadcast, {buf}, {buf}, n, dt, root, stream, 1.f);
+}
+
+void XgmiComm::reduce(const void* in, void* out, int64_t n, DType dt, int root, hipStream_t stream, float scale) {
+  run_rooted({this}, Rooted::Reduce, {in}, {out}, n, dt, root, stream, scale);
+}
+
+void XgmiComm::broadcast_local(const std::vector<XgmiComm*>& comms, const std::vector<void*>& bufs, int64_t n,
+                               DType dt, int root, hipStream_t stream) {
+  run_rooted(comms, Rooted::Broadcast, std::vector<const void*>(bufs.begin(), bufs.end()), bufs, n, dt, root, stream,
+             1.f);
+}
+
+void XgmiComm::reduce_local(const std::vector<XgmiComm*>& comms, const std::vector<const void*>& ins,
+                            const std::vector<void*>& outs, int64_t n, DType dt, int root, hipStream_t stream,
+                            float scale) {
+  run_rooted(comms, Rooted::Reduce, ins, outs, n, dt, root, stream, scale);
+}
+
 
 }  // namespace mxar

@@ -257,6 +257,18 @@ class XgmiComm {
                                const std::vector<void*>& outs, int64_t m, DType dt, hipStream_t stream,
                                float scale = 1.f);
 
+  // Rooted collectives (xgmi_rooted.hip), any n, one launch per segment of world * slot_bytes:
+  //   broadcast  buf[n] of `root` -> buf[n] of every rank (in place)
+  //   reduce     in[n] of every rank -> out[n] of `root` = scale * sum_s in_s (fp32, rank order,
+  //              one rounding); `out` is ignored off the root, in and out must not overlap on it
+  void broadcast(void* buf, int64_t n, DType dt, int root, hipStream_t stream);
+  void reduce(const void* in, void* out, int64_t n, DType dt, int root, hipStream_t stream, float scale = 1.f);
+  static void broadcast_local(const std::vector<XgmiComm*>& comms, const std::vector<void*>& bufs, int64_t n,
+                              DType dt, int root, hipStream_t stream);
+  static void reduce_local(const std::vector<XgmiComm*>& comms, const std::vector<const void*>& ins,
+                           const std::vector<void*>& outs, int64_t n, DType dt, int root, hipStream_t stream,
+                           float scale = 1.f);
+
   // Single-process cluster: ONE launch on `stream` runs every rank of `comms` (all on
   // one device, consecutive ranks, connected with connect_local); blockIdx.y = rank.
   static void allreduce_local(const std::vector<XgmiComm*>& comms, const std::vector<const void*>& ins,
@@ -340,6 +352,9 @@ class XgmiComm {
 
   static void run_coll(const std::vector<XgmiComm*>& group, Coll op, const std::vector<const void*>& ins,
                        const std::vector<void*>& outs, int64_t m, DType dt, hipStream_t stream, float scale);
+  static void run_rooted(const std::vector<XgmiComm*>& group, Rooted kind, const std::vector<const void*>& ins,
+                         const std::vector<void*>& outs, int64_t n, DType dt, int root, hipStream_t stream,
+                         float scale);
   // The fields every launch of `group` shares: membership, slab layout, timeout, fence, peers.
   CommArgs base_args(const std::vector<XgmiComm*>& group) const;
   // A grouped launch: connected, consecutive ranks on one device (need_rows: and one lag ring

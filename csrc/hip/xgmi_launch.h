@@ -28,5 +28,7 @@ void launch_ll(const CommArgs& a, dim3 grid, hipStream_t s, DType dt);
 void launch_adamw(const CommArgs& a, dim3 grid, hipStream_t s, DType dt);
 // Host entry of all-to-all (mode 0) / all-gather (1) / reduce-scatter (2) (xgmi_coll.hip).
 void launch_coll(const CommArgs& a, dim3 grid, hipStream_t s, DType dt, int mode);
+// Host entry of the rooted broadcast / reduce, root = a.root (xgmi_rooted.hip).
+void launch_rooted(const CommArgs& a, dim3 grid, hipStream_t s, DType dt, Rooted kind);
 
 }  // namespace mxar

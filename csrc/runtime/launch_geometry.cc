@@ -253,6 +253,40 @@ LaunchGeometry plan_coll(Coll op, const GridKnobs& k, int64_t n, int64_t es, int
   return g;
 }
 
+LaunchGeometry plan_rooted(Rooted kind, const GridKnobs& k, int64_t n, int64_t es, int ranks_here) {
+  LaunchGeometry g;
+  const int W = k.world;
+  const int Wm1 = std::max(1, W - 1);
+  const bool reduce = kind == Rooted::Reduce;
+  const int64_t elems = 16 / es, min_chunk = min_chunk_bytes() / es;
+  g.block = block_elems(W, n, es);
+  // the launch-size grid of plan_coll over the P blocks of every rank in the launch, within the
+  // shared-launch limits of the two-shot: all workgroups of the launch stay resident
+  int gdev = k.grid;
+  if (k.size_grid && k.grid == k.default_grid) {
+    const int64_t bytes = static_cast<int64_t>(ranks_here) * W * g.block * es;
+    const int64_t full_at = reduce ? (int64_t{1} << 30) : (int64_t{512} << 20);
+    gdev = size_grid_rule(bytes, k.grid, W, false, full_at);
+  }
+  const int gcap = std::min(per_rank(gdev, ranks_here), shared_launch_cap(k, ranks_here));
+  // ~one push unit per workgroup: a chunk goes to (or comes from) each of the P-1 peers
+  const int64_t target = std::max<int64_t>(1, gcap / Wm1);
+  g.chunk = std::max(min_chunk, round_up(ceil_div(g.block, target), elems));
+  g.nch = static_cast<int>(std::max<int64_t>(1, ceil_div(g.block, g.chunk)));
+  g.subchunk = g.chunk;
+  g.sub = 1;
+  if (reduce && g.nch <= k.maxch) {  // reduce units = push units, one flag column per reduce unit
+    const int64_t sub =
+        std::max<int64_t>(1, std::min<int64_t>({int64_t{Wm1}, g.chunk / min_chunk, k.maxch / g.nch}));
+    g.subchunk = round_up(ceil_div(g.chunk, sub), elems);
+    g.sub = static_cast<int>(ceil_div(g.chunk, g.subchunk));
+  }
+  g.gx = static_cast<int>(std::min<int64_t>(
+      gcap, std::max<int64_t>({1, int64_t{Wm1} * g.nch, static_cast<int64_t>(g.nch) * g.sub})));
+  check_slab(k, static_cast<int64_t>(g.nch) * g.sub, g.block * es);
+  return g;
+}
+
 int round_grid(const GridKnobs& k, int nch) {
   // one reduce unit per workgroup where possible, and the scatter / gather units (P - 1 per
   // chunk) spread over as many workgroups as there are, up to the grid: a round of few

@@ -118,6 +118,14 @@ LaunchGeometry plan_allreduce(Algo kind, const GridKnobs& k, int64_t n, int64_t 
 // One segment of n elements per block of a collective; `block` is the caller's (its m).
 LaunchGeometry plan_coll(Coll op, const GridKnobs& k, int64_t n, int64_t es, int ranks_here);
 
+// Rooted collectives (xgmi_rooted.hip): a broadcast is a scatter of the root's blocks plus an
+// all-gather, a reduce a reduce-scatter plus a gather to the root.
+enum class Rooted : int { Broadcast = 0, Reduce = 1 };
+// One segment of n elements in all (block = block_elems(world, n, es) per rank). Broadcast
+// chunks a block by plan_coll's all-gather rule, reduce by its reduce-scatter rule (each chunk
+// reduced in `sub` pieces, one flag column per piece).
+LaunchGeometry plan_rooted(Rooted kind, const GridKnobs& k, int64_t n, int64_t es, int ranks_here);
+
 // Elements per block of a two-shot style launch: ceil(n / world) rounded to 16 B.
 int64_t block_elems(int world, int64_t n, int64_t es);
 

@@ -31,7 +31,8 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from akka_allreduce_1_amd.parallel import BucketedGradReducer, TorchDistComm, XgmiCommunicator  # noqa: E402
+from akka_allreduce_1_amd.parallel import (BucketedGradReducer, TorchDistComm, XgmiCommunicator,  # noqa: E402
+                                           broadcast_parameters)
 from akka_allreduce_1_amd.parallel.comm import init_distributed  # noqa: E402
 
 
@@ -99,6 +100,7 @@ def main() -> int:
         comm = XgmiCommunicator(device=dev, max_lag=1 if args.th < 1.0 else None)
     kw = dict(th_reduce=args.th, th_complete=args.th, rescale=True) if args.th < 1.0 else {}
     overlap = {"on": True, "off": False, "auto": "auto"}[args.overlap]
+    broadcast_parameters(model, comm, src=0)  # replicas start as rank 0's, whatever each rank built or loaded
     reducer = BucketedGradReducer(model, comm, bucket_bytes=args.bucket_mib << 20, op="avg", overlap=overlap, **kw)
     opt = torch.optim.AdamW(model.parameters(), lr=args.lr)
     gen = torch.Generator().manual_seed(1000 + rank)
