@@ -730,6 +730,7 @@ void bind_hip(py::module_& m) {
       .def_property_readonly("alloc_bytes", &XgmiComm::alloc_bytes)
       .def_property_readonly("connected", &XgmiComm::connected)
       .def_property_readonly("stats", &XgmiComm::stats)
+      .def_property_readonly("knobs", &XgmiComm::knobs, "what the launch planner reads of this communicator (a copy)")
       .def_property("fence", &XgmiComm::fence, &XgmiComm::set_fence)
       .def_property("units_per_wg", &XgmiComm::units_per_wg, &XgmiComm::set_units_per_wg)
       .def_property("ring_depth", &XgmiComm::ring_depth, &XgmiComm::set_ring_depth)
