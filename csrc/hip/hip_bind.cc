@@ -460,6 +460,81 @@ void bind_hip(py::module_& m) {
   h.def("sdma_copy_probe", &sdma_copy_probe, py::arg("device"), py::arg("dst"), py::arg("src"), py::arg("bytes"),
         py::arg("engine") = 0, py::arg("iters") = 10, py::arg("nengines") = 1, py::call_guard<py::gil_scoped_release>());
   h.def("pci_location", &pci_location, py::arg("device"));
+  // The copy-engine allreduce's pure schedule (csrc/runtime/sdma_schedule.h), for CPU tests.
+  h.def(
+      "plan_sdma_segment",
+      [](int world, int64_t n, int64_t es, int64_t slot_bytes, int pieces) {
+        const SdmaSegment s = plan_sdma_segment(world, n, es, slot_bytes, pieces);
+        py::dict d;
+        d["block"] = s.block;
+        d["pe"] = s.pe;
+        d["K"] = s.K;
+        return d;
+      },
+      py::arg("world"), py::arg("n"), py::arg("elem_size"), py::arg("slot_bytes"), py::arg("pieces") = 0);
+  h.def(
+      "plan_sdma_copies",
+      [](int world, int rank, int64_t n, int64_t es, int epp, int64_t slot_bytes, int pieces, int par) {
+        const SdmaSegment seg = plan_sdma_segment(world, n, es, slot_bytes, pieces);
+        const SdmaSchedule s = plan_sdma_copies(seg, world, rank, es, epp, slot_bytes, par);
+        auto sig = [&](SdmaSigRef r) -> std::string {
+          const std::string i = std::to_string(r.index);
+          switch (r.kind) {
+            case SdmaSig::Start: return "start";
+            case SdmaSig::Mid: return "mid[" + i + "]";
+            case SdmaSig::C1: return "c1[" + std::to_string(r.index / seg.K) + "," + std::to_string(r.index % seg.K) + "]";
+            case SdmaSig::C2: return "c2[" + i + "]";
+            case SdmaSig::Scf: return "scf";
+            default: return "gdf";
+          }
+        };
+        py::list copies;
+        int64_t bytes = 0;
+        for (const SdmaCopy& c : s.copies) {
+          py::dict e;
+          e["dst_rank"] = c.dst_rank;
+          e["dst_off"] = c.dst_off;
+          e["src"] = c.src == SdmaSrc::In ? "in" : c.src == SdmaSrc::Out ? "out" : "epoch";
+          e["src_off"] = c.src_off;
+          e["bytes"] = c.bytes;
+          e["dep"] = sig(c.dep);
+          e["done"] = sig(c.done);
+          e["peer"] = c.peer;
+          e["engine"] = c.engine;
+          copies.append(e);
+          bytes += c.bytes;
+        }
+        py::dict d;
+        d["block"] = seg.block;
+        d["pe"] = seg.pe;
+        d["K"] = seg.K;
+        d["c1"] = s.c1;
+        d["c2"] = s.c2;
+        d["scf"] = s.scf;
+        d["gdf"] = s.gdf;
+        d["copies"] = copies;
+        d["bytes"] = bytes;
+        return d;
+      },
+      py::arg("world"), py::arg("rank"), py::arg("n"), py::arg("elem_size"), py::arg("engines_per_peer"),
+      py::arg("slot_bytes"), py::arg("pieces") = 0, py::arg("par") = 0,
+      "one rank's engine copies of one segment, in submission order, and the arm value of every signal");
+  h.def(
+      "sdma_parts",
+      [](int64_t bytes, int epp) {
+        const SdmaParts p = sdma_parts(bytes, epp);
+        std::vector<std::pair<int64_t, int64_t>> out;
+        for (int i = 0; i < p.count; ++i) out.emplace_back(p.off(i), p.len(i));
+        return out;
+      },
+      py::arg("bytes"), py::arg("engines_per_peer"), "(offset, length) of each part, part p on engine p");
+  h.def("sdma_pick_engines", &sdma_pick_engines, py::arg("avail_mask"), py::arg("allowed"), py::arg("k"),
+        py::arg("engines_per_peer"));
+  h.def("sdma_engine_share", &sdma_engine_share, py::arg("local_engines"), py::arg("nloc"), py::arg("rank"));
+  h.def("sdma_auto_epp", &sdma_auto_epp, py::arg("n_engines"), py::arg("world"));
+  h.def("sdma_slot_bytes", &sdma_slot_bytes, py::arg("requested"));
+  h.def("sdma_slab_bytes", &sdma_slab_bytes, py::arg("world"), py::arg("slot_bytes"));
+  h.def("sdma_segment_elems", &sdma_segment_elems, py::arg("world"), py::arg("slot_bytes"), py::arg("elem_size"));
   py::class_<SdmaComm>(h, "SdmaComm")
       .def(py::init<int, int, int, int64_t, int, int, double>(), py::arg("rank"), py::arg("world"), py::arg("device"),
            py::arg("slot_bytes"), py::arg("grid") = 32, py::arg("engines_per_peer") = 0, py::arg("timeout_s") = 20.0)

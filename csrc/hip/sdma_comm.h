@@ -34,12 +34,10 @@
 #include <string>
 #include <vector>
 
+#include "../runtime/sdma_schedule.h"
 #include "xgmi_comm.h"
 
 namespace mxar {
-
-constexpr int kSdmaMaxPieces = 8;  // pipeline pieces per block at most
-constexpr int kSdmaMaxLocal = 8;   // local ranks one reduce / gather launch serves
 
 struct SdmaStats {
   uint64_t calls = 0, copies = 0, bytes = 0, host_waits = 0;
@@ -82,7 +80,7 @@ class SdmaComm {
   // profiles/round6/sdma_pipe_*.jsonl: 2 pieces at 32-128 MiB blocks, grid 128)
   int pieces() const { return pieces_; }
   void set_pieces(int k) { pieces_ = k < 0 ? 0 : k; }
-  int engines() const { return static_cast<int>(local_engines_.size()); }
+  int engines() const;
   int engines_per_peer() const { return epp_; }
   int64_t slot_bytes() const { return slot_bytes_; }
   const SdmaStats& stats() const { return st_; }
@@ -92,31 +90,27 @@ class SdmaComm {
   struct Plan {
     const char* in = nullptr;
     char* out = nullptr;
-    int64_t n = 0, block = 0, pe = 0;  // pe: elements per pipeline piece
-    int K = 1;                         // pipeline pieces of a block
-    DType dt = DType::F32;
+    SdmaSegment seg;
     uint32_t epoch = 0;
     int par = 0, slot = 0;
   };
-  // one segment: wait for the slot, arm its signals, queue both phases' copies (host)
-  Plan plan(const char* in, char* out, int64_t n, DType dt);
+  // one segment of n elements of `es` bytes: wait for the slot, arm its signals, queue both
+  // phases' copies (host)
+  Plan plan(const char* in, char* out, int64_t n, int64_t es);
   int rank_, world_, device_;
   int64_t slot_bytes_;
   int grid_;
   int epp_;
   int pieces_ = 0;
-  uint32_t* cnt_ = nullptr;  // device: per-piece workgroup tickets of the reduce kernel
   double timeout_s_;
-  char* slab_ = nullptr;
   int64_t slab_bytes_ = 0;
-  uint32_t* err_ = nullptr;  // device error word
   std::vector<char*> peers_;
   std::vector<bool> opened_;
-  std::vector<uint32_t> local_engines_;
+  uint32_t engines_ = 0;  // mask of the engines this rank submits to
   uint64_t epoch_ = 0;
   bool connected_ = false;
   SdmaStats st_;
-  std::unique_ptr<Impl> impl_;
+  std::unique_ptr<Impl> impl_;  // HSA and device resources, each with its owner
 };
 
 // HSA view of the machine (agents, PCI locations, SDMA engine masks): bring-up diagnostics

@@ -30,6 +30,7 @@
 #include "../runtime/loopback_plane.h"
 #include "../runtime/plane_rounds.h"
 #include "../runtime/plane_worker.h"
+#include "../runtime/sdma_schedule.h"
 
 using namespace mxar;
 
@@ -664,6 +665,134 @@ static int run_geometry(int iters) {
   return 0;
 }
 
+// The copy-engine allreduce's schedule (sdma_schedule.cc) over pseudo-random shapes: what the
+// engines (in-order queues, one dependency per copy, signals armed to a count) and the reduce /
+// gather kernels (the flag words they wait on) rely on; the arithmetic never overflows (UBSan).
+static int run_sdma(int iters) {
+  uint64_t state = 0xD1B54A32D192ED03ull;
+  auto rnd = [&state](uint64_t lo, uint64_t hi) {  // xorshift64*, fixed seed
+    state ^= state >> 12;
+    state ^= state << 25;
+    state ^= state >> 27;
+    return lo + (state * 0x2545F4914F6CDD1Dull >> 11) % (hi - lo + 1);
+  };
+  int failures = 0;
+  int64_t copies = 0;
+  for (int it = 0; it < iters; ++it) {
+    const int W = static_cast<int>(rnd(0, 3) ? rnd(1, 8) : rnd(1, kSdmaMaxWorld));
+    const int64_t es = rnd(0, 1) ? 2 : 4;
+    const int64_t slot = sdma_slot_bytes(static_cast<int64_t>((uint64_t{1} << rnd(10, 29)) + (rnd(0, 1) ? rnd(0, 70000) : 0)));
+    const int pieces = static_cast<int>(rnd(0, 9)), epp = static_cast<int>(rnd(1, 5)), par = static_cast<int>(rnd(0, 1));
+    const int64_t segn = sdma_segment_elems(W, slot, es);
+    const int64_t n = rnd(0, 3) == 0 ? segn - static_cast<int64_t>(rnd(0, 1))
+                                     : static_cast<int64_t>(rnd(1, std::min<uint64_t>(segn, uint64_t{1} << rnd(0, 34))));
+    auto check = [&](bool ok, const char* what, int r) {
+      if (ok) return;
+      if (failures++ < 10)
+        std::fprintf(stderr, "sdma: %s violated (world %d rank %d n %lld es %lld slot %lld pieces %d epp %d par %d)\n",
+                     what, W, r, static_cast<long long>(n), static_cast<long long>(es), static_cast<long long>(slot),
+                     pieces, epp, par);
+    };
+    const SdmaSegment g = plan_sdma_segment(W, std::max<int64_t>(n, 1), es, slot, pieces);  // n <= segment: never throws
+    const int K = g.K;
+    check(K >= 1 && K <= kSdmaMaxPieces && (g.pe * es) % 4096 == 0 && (g.block * es) % 16 == 0, "K, piece alignment", -1);
+    check(g.block * es <= slot && g.block * W >= g.n && static_cast<int64_t>(K) * g.pe >= g.block, "blocks cover n in slots", -1);
+    const int64_t slab = sdma_slab_bytes(W, slot);
+    // flag words each rank's slab receives, over all ranks' schedules
+    std::vector<std::vector<int>> written(W, std::vector<int>(2 * kFrWord, 0));
+    SdmaSchedule sc;
+    for (int r = 0; r < W; ++r) {
+      sc = plan_sdma_copies(g, W, r, es, epp, slot, par, std::move(sc));
+      copies += static_cast<int64_t>(sc.copies.size());
+      std::vector<int64_t> next1(W, 0), next2(W, 0);
+      std::vector<int> c1(static_cast<size_t>(W) * K, 0), c2(K, 0), flagged1(static_cast<size_t>(W) * K, 0), flagged2(K, 0);
+      int scf = 0, gdf = 0;
+      const SdmaCopy* prev = nullptr;
+      for (const SdmaCopy& c : sc.copies) {
+        const bool flag = c.src == SdmaSrc::Epoch;
+        check(c.dst_rank >= 0 && c.dst_rank < W && c.bytes > 0 && c.dst_off >= 0 && c.dst_off + c.bytes <= slab, "inside the slab", r);
+        check(c.peer >= 0 && c.peer < W && c.peer != r && c.engine >= 0 && c.engine < epp, "an engine towards a peer", r);
+        if (!flag && c.src == SdmaSrc::In) {  // phase 1: block j, in order, to rank j's SD[par][r]
+          const int j = c.dst_rank;
+          int64_t& at = next1[j];
+          const int k = static_cast<int>(at / (g.pe * es));
+          check(j != r && c.peer == j && c.src_off == j * g.block * es + at && c.dst_off == sdma_sd_off(W, slot, par, r) + at,
+                "phase-1 part continues block j", r);
+          check(at % 4096 == 0 && at + c.bytes <= slot && at + c.bytes <= (k + 1) * g.pe * es, "4 KiB aligned inside its piece and slot", r);
+          check(c.dep.kind == SdmaSig::Start && c.done.kind == SdmaSig::C1 && c.done.index == j * K + k, "phase-1 signals", r);
+          check(flagged1[static_cast<size_t>(j) * K + k] == 0, "no phase-1 part behind its flag", r);
+          ++c1[static_cast<size_t>(j) * K + k];
+          at += c.bytes;
+        } else if (!flag) {  // phase 2: the own block to rank q's RD[par][r]
+          const int q = c.dst_rank;
+          int64_t& at = next2[q];
+          const int k = static_cast<int>(at / (g.pe * es));
+          check(q != r && c.peer == q && c.src == SdmaSrc::Out && c.src_off == r * g.block * es + at &&
+                    c.dst_off == sdma_rd_off(W, slot, par, r) + at, "phase-2 part continues the own block", r);
+          check(at % 4096 == 0 && at + c.bytes <= slot && at + c.bytes <= (k + 1) * g.pe * es, "4 KiB aligned inside its piece and slot", r);
+          check(c.dep.kind == SdmaSig::Mid && c.dep.index == k && c.done.kind == SdmaSig::C2 && c.done.index == k, "phase-2 signals", r);
+          check(flagged2[k] == 0, "every part of a piece is queued before any of its flags", r);
+          ++c2[k];
+          at += c.bytes;
+        } else {
+          check(c.bytes == 4 && c.dst_off % 4 == 0 && c.dst_off + 4 <= kFlagBytes && c.src_off == 0, "a flag word", r);
+          ++written[c.dst_rank][static_cast<size_t>(std::min<int64_t>(c.dst_off / 4, 2 * kFrWord - 1))];
+          if (c.done.kind == SdmaSig::Scf) {  // FS[r][k] in rank j's slab, behind the piece's last part
+            const int j = c.dst_rank, k = c.dep.index % K;
+            check(c.dep.kind == SdmaSig::C1 && c.dep.index == j * K + k && c.dst_off == 4 * sdma_fs_word(r, k), "FS flag", r);
+            check(prev && prev->src == SdmaSrc::In && prev->done.kind == SdmaSig::C1 && prev->done.index == c.dep.index &&
+                      prev->peer == c.peer && prev->engine == c.engine, "FS rides the engine of its piece's last part", r);
+            ++flagged1[static_cast<size_t>(c.dep.index)];
+            ++scf;
+          } else {
+            const int k = c.dep.index;
+            check(c.done.kind == SdmaSig::Gdf && c.dep.kind == SdmaSig::C2 && k < K && c.dst_off == 4 * sdma_fr_word(r, k), "FR flag", r);
+            ++flagged2[k];
+            ++gdf;
+          }
+        }
+        prev = &c;
+      }
+      for (int j = 0; j < W; ++j) {
+        check(next1[j] == (j == r ? 0 : sdma_block_len(g.n, g.block, j) * es), "phase 1 tiles block j exactly once", r);
+        check(next2[j] == (j == r ? 0 : sdma_block_len(g.n, g.block, r) * es), "phase 2 tiles the own block once per peer", r);
+      }
+      check(c1 == sc.c1 && c2 == sc.c2 && scf == sc.scf && gdf == sc.gdf, "arm value = copies completing into the signal", r);
+      for (int k = 0; k < K; ++k) check(sc.c1[static_cast<size_t>(r) * K + k] == 0, "c1[r, *] = 0", r);
+    }
+    // the words the kernels of rank t wait on (sdma_reduce_kernel, sdma_gather_kernel)
+    for (int t = 0; t < W; ++t) {
+      std::vector<int> waited(2 * kFrWord, 0);
+      const int64_t rl = sdma_block_len(g.n, g.block, t);
+      for (int k = 0; k < K && sdma_block_len(rl, g.pe, k) > 0; ++k)
+        for (int s = 0; s < W; ++s)
+          if (s != t) ++waited[static_cast<size_t>(sdma_fs_word(s, k))];
+      for (int k = 0; k < K && W > 1 && static_cast<int64_t>(k) * g.pe < g.block; ++k)
+        for (int s = 0; s < W; ++s)
+          if (sdma_block_len(g.n, g.block, s) > static_cast<int64_t>(k) * g.pe) ++waited[static_cast<size_t>(sdma_fr_word(s, k))];
+      check(waited == written[t], "the flags sent are the flags the kernels wait on", t);
+    }
+  }
+  if (failures != 0 || copies < iters) {
+    std::fprintf(stderr, "sdma: %d violations, %lld copies planned\n", failures, static_cast<long long>(copies));
+    return 1;
+  }
+  // the 4 KiB split on its own
+  for (int i = 0; i < 20000; ++i) {
+    const int64_t bytes = static_cast<int64_t>(rnd(0, uint64_t{1} << rnd(0, 40)));
+    const int epp = static_cast<int>(rnd(1, 16));
+    const SdmaParts p = sdma_parts(bytes, epp);
+    int64_t at = 0;
+    for (int e = 0; e < p.count; ++e) {
+      if (p.off(e) != at || at % 4096 != 0 || p.len(e) <= 0) ++failures;
+      at += p.len(e);
+    }
+    if (at != bytes || p.count > epp) ++failures;
+  }
+  if (failures != 0) std::fprintf(stderr, "sdma: %d split checks failed\n", failures);
+  return failures != 0;
+}
+
 // The round plane's host bookkeeping (plane_rounds.h): the slot ring and the lock-free hand-off
 // between a launching and a completion thread, and the decoding of a finished slot.
 static int run_rounds(int records) {
@@ -777,6 +906,7 @@ int main(int argc, char** argv) {
   const std::string only = argc > 1 ? argv[1] : "";
   int rc = 0;
   if (only.empty() || only == "geometry") rc = run_geometry(4000);
+  if (rc == 0 && (only.empty() || only == "sdma")) rc = run_sdma(1500);
   if (rc == 0 && (only.empty() || only == "rounds")) rc = run_rounds(5000);
   if (rc == 0 && (only.empty() || only == "mailbox")) rc = run_mailbox(6, 20000);
   if (rc == 0 && (only.empty() || only == "local")) rc = run_local(4, 37, 3, 30);

@@ -207,3 +207,37 @@ def test_sdma_xdev_children_validate():
         t.join()
     assert all(r and r.get("validated") for r in rows), rows
     assert all(r.get("p50_ms", 0) > 0 for r in rows), rows
+
+
+def test_submitted_copies_are_the_planned_schedule():
+    """Ties the CPU-tested schedule (tests/test_sdma_schedule.py) to what SdmaComm submits: after
+    each call every rank's copy and byte counters moved by exactly the count and byte total of
+    hip.plan_sdma_copies for that rank and each segment; integer-valued fp32, so the sum is exact."""
+    from akka_allreduce_1_amd._native import C
+    from akka_allreduce_1_amd.parallel import LocalSdmaCluster
+
+    P, slot = 3, 64 << 10
+    cl = LocalSdmaCluster(P, slot_bytes=slot, grid=4)
+    for c in cl.comms:
+        c.pieces = 3
+    seg = P * (slot // 4)
+    epoch = 0
+    for n in (4096 + 5, seg + 7):  # one segment, then two
+        xs = [torch.randint(-1000, 1000, (n,), generator=torch.Generator().manual_seed(n + k)).float().to(DEV)
+              for k in range(P)]
+        before = [dict(c.stats) for c in cl.comms]
+        ys = cl.allreduce(xs)
+        torch.cuda.synchronize()
+        cl.check()
+        lens = [min(seg, n - off) for off in range(0, n, seg)]
+        for r, c in enumerate(cl.comms):
+            plans = [C.hip.plan_sdma_copies(P, r, m, 4, c.engines_per_peer, c.slot_bytes, 3, (epoch + 1 + i) & 1)
+                     for i, m in enumerate(lens)]
+            assert all(len(p["copies"]) > 0 for p in plans)
+            assert c.stats["calls"] - before[r]["calls"] == len(lens) == (1 if n <= seg else 2)
+            assert c.stats["copies"] - before[r]["copies"] == sum(len(p["copies"]) for p in plans)
+            assert c.stats["bytes"] - before[r]["bytes"] == sum(p["bytes"] for p in plans)
+        epoch += len(lens)
+        ref = xs[0] + xs[1] + xs[2]
+        for y in ys:
+            assert torch.equal(y, ref)

@@ -16,6 +16,8 @@ experiments (every cell validated against an fp32 sum before it is timed):
   ring       8 logical ranks x 256 MiB: fp32-wire ring, element-type ring, two-shot, p50 and
              fraction of the same process's copy roofline
   sdma       the copy-engine allreduce at several reduce grids (--grids)
+  sdma-host  the copy-engine allreduce's host side: p50 device time per call, wall time per call
+             and the median host time inside a call (--ranks, --mibs), bf16
   sdma-remap the copy-engine allreduce before / after its input (x), output (y) or both
              were freed, the cache emptied and re-allocated at the same addresses, and with
              the input staged through a buffer allocated first (--mode x|y|both)
@@ -208,6 +210,52 @@ def exp_sdma(a) -> None:
             torch.cuda.empty_cache()
 
 
+def exp_sdma_host(a) -> None:
+    import time
+
+    import torch
+
+    from akka_allreduce_1_amd.ops import fill_uniform
+    from akka_allreduce_1_amd.parallel import LocalSdmaCluster
+    from akka_allreduce_1_amd.utils.timing import percentile
+    from benchmarks.sections import device_times, rounding_check, wall_per_call
+
+    dev = torch.device("cuda", 0)
+    dtype = torch.bfloat16
+    for P in [int(x) for x in a.ranks.split(",")]:
+        for mib in [int(x) for x in a.mibs.split(",")]:
+            nbytes = mib << 20
+            n = nbytes // 2
+            xs = [fill_uniform(torch.empty(n, dtype=dtype, device=dev), seed=900 + k) for k in range(P)]
+            ys = [torch.empty_like(x) for x in xs]
+            ref = torch.zeros(n, device=dev)
+            for x in xs:
+                ref += x.float()
+            cl = LocalSdmaCluster(P, slot_bytes=-(-nbytes // P) + (1 << 20), timeout_s=20.0)
+            cl.allreduce(xs, ys)
+            torch.cuda.synchronize(dev)
+            cl.check()
+            ok, err, _ = rounding_check(ys, ref, dtype, P)
+            for rep in range(a.reps):
+                p50 = percentile(device_times(lambda: cl.allreduce(xs, ys), a.iters, dev), 50)
+                wall = wall_per_call(lambda: cl.allreduce(xs, ys), a.iters, dev)
+                host = []
+                for _ in range(a.iters):  # the engines idle: nothing to wait for, submission alone
+                    torch.cuda.synchronize(dev)
+                    t0 = time.perf_counter()
+                    cl.allreduce(xs, ys)
+                    host.append(time.perf_counter() - t0)
+                torch.cuda.synchronize(dev)
+                cl.check()
+                _emit({"exp": "sdma-host", "tag": a.tag, "rep": rep, "P": P, "mib": mib,
+                       "engines_per_peer": cl.comms[0].engines_per_peer, "copies_per_call":
+                       sum(c.stats["copies"] for c in cl.comms) // max(1, cl.comms[0].stats["calls"]),
+                       "validated": ok, "max_abs_err": err, "p50_ms": round(p50, 4), "wall_ms": round(wall * 1e3, 4),
+                       "host_us": round(statistics.median(host) * 1e6, 1)})
+            del cl, xs, ys, ref
+            torch.cuda.empty_cache()
+
+
 def exp_sdma_remap(a) -> None:
     import torch
 
@@ -347,6 +395,11 @@ def main() -> None:
     p.add_argument("--pieces", default="0", help="pipeline pieces per block (0 = by size)")
     p.add_argument("--reps", type=int, default=2)
     p.add_argument("--iters", type=int, default=10)
+    p = sub.add_parser("sdma-host")
+    p.add_argument("--ranks", default="2,8")
+    p.add_argument("--mibs", default="1,256")
+    p.add_argument("--reps", type=int, default=3)
+    p.add_argument("--iters", type=int, default=20)
     p = sub.add_parser("sdma-remap")
     p.add_argument("--P", type=int, default=2)
     p.add_argument("--mib", type=int, default=256)
@@ -360,7 +413,7 @@ def main() -> None:
         s.add_argument("--tag", default="")
     a = ap.parse_args()
     _setup(a.env)
-    {"threshold": exp_threshold, "protocol": exp_protocol, "plane-paths": exp_plane_paths, "ring": exp_ring, "sdma": exp_sdma, "sdma-remap": exp_sdma_remap, "grid": exp_grid,
+    {"threshold": exp_threshold, "protocol": exp_protocol, "plane-paths": exp_plane_paths, "ring": exp_ring, "sdma": exp_sdma, "sdma-host": exp_sdma_host, "sdma-remap": exp_sdma_remap, "grid": exp_grid,
      "coll-grid": exp_coll_grid}[a.exp](a)
 
 
