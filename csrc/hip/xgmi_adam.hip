@@ -33,6 +33,12 @@ __device__ __forceinline__ float adamw(float g, float* p, float* m, float* v, co
   const float vv = a.beta2 * *v + (1.f - a.beta2) * g * g;
   const float denom = sqrtf(vv) / a.c2_sqrt + a.eps;
   pv -= (a.lr / a.c1) * mv / denom;
+  // The callers round the returned value to the parameter dtype: it must be the fp32 value the
+  // master holds. Left to itself the compiler folds the last multiply-subtract and the fp16
+  // conversion of the scalar tail into one v_fma_mixlo_f16, which rounds the unrounded result
+  // straight to fp16 - at a tie of the fp32 value a parameter one fp16 ulp off master.to(fp16)
+  // (tests/test_adamw_gpu.py). The empty asm pins pv as an fp32 register value; no instruction.
+  asm("" : "+v"(pv));
   *p = pv;
   *m = mv;
   *v = vv;
