@@ -122,6 +122,41 @@ def init_distributed(backend: str = "nccl") -> tuple[int, int, int]:
     return rank, world, local
 
 
+def sq_record(sqs) -> torch.Tensor:
+    """The 16-byte record a rank contributes to a global gradient norm: float64 [2], [0] = the
+    rank's sums of squares (device scalars, one per bucket) added in bucket order, [1] = 0."""
+    sqs = [sqs] if isinstance(sqs, torch.Tensor) else list(sqs)
+    rec = torch.zeros(2, dtype=torch.float64, device=sqs[0].device)
+    total = sqs[0].reshape(1).double()
+    for s in sqs[1:]:
+        total = total + s.reshape(1).double()
+    rec[:1] = total
+    return rec
+
+
+def clip_coef_from_records(recs: torch.Tensor, max_norm: float) -> tuple[torch.Tensor, torch.Tensor]:
+    """recs: float64 [world, 2], the ranks' `sq_record`s in rank order. Adds them in rank order in
+    float64 and returns (total_norm, coef), 0-d fp32: total_norm = sqrt(total), coef = min(1,
+    max_norm / (total_norm + 1e-6)) evaluated in fp32 as torch.nn.utils.clip_grad_norm_ does (an
+    inf norm gives 0, a NaN norm NaN). Plain torch ops on the current stream, no host sync."""
+    total = recs[0, 0]
+    for k in range(1, recs.shape[0]):
+        total = total + recs[k, 0]
+    norm = total.sqrt().to(torch.float32)
+    coef = (float(max_norm) / (norm + 1e-6)).clamp(max=1.0)
+    return norm, coef
+
+
+def gather_sq_records(comm, rec: torch.Tensor) -> torch.Tensor:
+    """All-gather one `sq_record` per rank through `comm.all_gather` (as 4 fp32 words: every
+    communicator carries those; the bits are what matters) -> float64 [world, 2]."""
+    if comm.world == 1:
+        return rec.view(1, 2)
+    out = torch.empty(4 * comm.world, dtype=torch.float32, device=rec.device)
+    comm.all_gather(rec.view(torch.float32), out)
+    return out.view(torch.float64).view(comm.world, 2)
+
+
 class XgmiCommunicator:
     """Allreduce over directly mapped peer HBM for the ranks of a torch.distributed group."""
 
@@ -605,6 +640,16 @@ class XgmiCommunicator:
         `grid` > 0 overrides the workgroup count (fewer leave CUs to overlapped GEMMs)."""
         if grads.numel() != params.numel() or grads.dtype != params.dtype:
             raise ValueError("grads and params must match in size and dtype")
+        self._step_grid(grid)
+        h = _H.AdamW()
+        h.lr, (h.beta1, h.beta2), h.eps, h.weight_decay, h.step = lr, betas, eps, weight_decay, step
+        self._c.step_adamw(grads.data_ptr(), params.data_ptr(), params.numel(), _dtype_code(params.dtype),
+                           _current_stream(self._dev), state["master"].data_ptr(), state["exp_avg"].data_ptr(),
+                           state["exp_avg_sq"].data_ptr(), h, 1.0 / self.world if op == "avg" else 1.0)
+        return params
+
+    def _step_grid(self, grid: int) -> None:
+        """The launch knobs of the fused step and its clipped halves: `grid` or the default."""
         g = grid if grid > 0 else self._default_grid
         if self._grid != g:
             self._c.grid = g
@@ -615,11 +660,54 @@ class XgmiCommunicator:
         if self._units != self._default_units:  # a tuned "~1" two-shot label must not leak in here
             self._c.units_per_wg = self._default_units
             self._units = self._default_units
+
+    # -------------------------------------------------- the clipped step (csrc/hip/xgmi_clip.hip)
+    def gshard(self, params: torch.Tensor) -> torch.Tensor:
+        """Scratch for the clipped step: the fp32 gradient shard of `params` (shard_len elements)."""
+        return torch.zeros(self.shard_len(params.numel(), params.dtype), dtype=torch.float32, device=self.device)
+
+    def reduce_scatter_sq(self, grads: torch.Tensor, gshard: torch.Tensor, *, op: str = "avg",
+                          grid: int = 0) -> torch.Tensor:
+        """First half of the clipped step, one launch: reduce-scatter `grads` (mean by default;
+        fp32, rank order) into `gshard` (fp32, `shard_len(n)` elements, block `rank`) and return
+        the sum of the squares of this rank's shard as a device fp32 scalar (fixed summation
+        tree: the same bits whatever order the workgroups arrive in). `grads` is not written."""
+        if op not in ("sum", "avg"):
+            raise ValueError(f"unsupported op {op!r}")
+        if gshard.dtype != torch.float32 or gshard.numel() != self.shard_len(grads.numel(), grads.dtype):
+            raise ValueError("gshard must hold shard_len(n) fp32 elements")
+        if not (grads.is_contiguous() and gshard.is_contiguous()):
+            raise ValueError("tensors must be contiguous")
+        self._step_grid(grid)
+        sq = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self._c.reduce_scatter_sq(grads.data_ptr(), gshard.data_ptr(), sq.data_ptr(), grads.numel(),
+                                  _dtype_code(grads.dtype), _current_stream(self._dev),
+                                  1.0 / self.world if op == "avg" else 1.0)
+        return sq
+
+    def clip_coef(self, sqs, max_norm: float) -> tuple[torch.Tensor, torch.Tensor]:
+        """(total_norm, coef), 0-d fp32 device tensors, from this rank's sums of squares (one
+        per bucket, in bucket order): one 16-byte record per rank is all-gathered and the P
+        records are added in rank order in float64, so `coef` has the same bits on every rank.
+        coef = min(1, max_norm / (total_norm + 1e-6)). No host sync."""
+        return clip_coef_from_records(gather_sq_records(self, sq_record(sqs)), max_norm)
+
+    def step_adamw_shard(self, gshard: torch.Tensor, params: torch.Tensor, state: dict, *, coef: torch.Tensor,
+                         lr: float, betas: tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
+                         weight_decay: float = 0.0, step: int, grid: int = 0) -> torch.Tensor:
+        """Second half of the clipped step, one launch: AdamW on this rank's shard state with
+        `gshard[i] * coef` as the gradient (`coef`: a 1-element fp32 device tensor), then the
+        all-gather of the new `params` - the fused step from its optimizer on."""
+        if coef.dtype != torch.float32 or coef.numel() != 1 or coef.get_device() != self._dev:
+            raise ValueError(f"coef must be a 1-element fp32 tensor on {self.device}")
+        if gshard.dtype != torch.float32 or gshard.numel() != self.shard_len(params.numel(), params.dtype):
+            raise ValueError("gshard must hold shard_len(n) fp32 elements")
+        self._step_grid(grid)
         h = _H.AdamW()
         h.lr, (h.beta1, h.beta2), h.eps, h.weight_decay, h.step = lr, betas, eps, weight_decay, step
-        self._c.step_adamw(grads.data_ptr(), params.data_ptr(), params.numel(), _dtype_code(params.dtype),
-                           _current_stream(self._dev), state["master"].data_ptr(), state["exp_avg"].data_ptr(),
-                           state["exp_avg_sq"].data_ptr(), h, 1.0 / self.world if op == "avg" else 1.0)
+        self._c.step_adamw_shard(gshard.data_ptr(), coef.data_ptr(), params.data_ptr(), params.numel(),
+                                 _dtype_code(params.dtype), _current_stream(self._dev), state["master"].data_ptr(),
+                                 state["exp_avg"].data_ptr(), state["exp_avg_sq"].data_ptr(), h)
         return params
 
     def shard_len(self, n: int, dtype: torch.dtype) -> int:
@@ -889,6 +977,66 @@ class LocalCluster:
                 code, torch.cuda.current_stream(dev).cuda_stream,
                 [(states[k]["master"].data_ptr(), states[k]["exp_avg"].data_ptr(), states[k]["exp_avg_sq"].data_ptr())
                  for k in g], h, 1.0 / self.world if op == "avg" else 1.0)
+
+    def reduce_scatter_sq(self, grads: Sequence[torch.Tensor], gshards: Sequence[torch.Tensor], *,
+                          op: str = "avg") -> list[torch.Tensor]:
+        """First half of the clipped step for every logical rank (xgmi_clip.hip); returns the
+        ranks' sums of squares, one device fp32 scalar each."""
+        n = grads[0].numel()
+        code = _dtype_code(grads[0].dtype)
+        self._check_shards(grads, gshards, n, code)
+        sqs = [torch.zeros(1, dtype=torch.float32, device=self.devices[k]) for k in range(self.world)]
+        for g in self.groups:
+            dev = self.devices[g[0]]
+            _H.XgmiComm.reduce_scatter_sq_local(
+                [self.comms[k] for k in g], [grads[k].data_ptr() for k in g], [gshards[k].data_ptr() for k in g],
+                [sqs[k].data_ptr() for k in g], n, code, torch.cuda.current_stream(dev).cuda_stream,
+                1.0 / self.world if op == "avg" else 1.0)
+        return sqs
+
+    def _check_shards(self, full, gshards, n: int, code) -> None:
+        b = self.comms[0].block_elems(n, code)
+        if len(full) != self.world or len(gshards) != self.world:
+            raise ValueError("one tensor and one gshard per logical rank")
+        for k in range(self.world):
+            x, g = full[k], gshards[k]
+            if x.numel() != n or x.dtype != full[0].dtype or not x.is_contiguous() or x.device != self.devices[k]:
+                raise ValueError(f"rank {k}: contiguous tensors of one shape and dtype on {self.devices[k]}")
+            if g.dtype != torch.float32 or g.numel() != b or not g.is_contiguous() or g.device != self.devices[k]:
+                raise ValueError(f"rank {k}: gshard must hold block_elems(n) = {b} contiguous fp32 elements")
+
+    def clip_coef(self, sqs: Sequence, max_norm: float) -> tuple[list[torch.Tensor], list[torch.Tensor]]:
+        """sqs[k]: rank k's sum of squares, or its list of them in bucket order. Every rank's
+        16-byte record goes through the all-gather kernel; returns (total_norms, coefs), one 0-d
+        fp32 tensor per rank (see XgmiCommunicator.clip_coef)."""
+        recs = [sq_record(s) for s in sqs]
+        if self.world == 1:
+            outs = recs
+        else:
+            outs = self.collective("all_gather", [r.view(torch.float32) for r in recs])
+        res = [clip_coef_from_records(o.view(torch.float64).view(self.world, 2), max_norm) for o in outs]
+        return [r[0] for r in res], [r[1] for r in res]
+
+    def step_adamw_shard(self, gshards: Sequence[torch.Tensor], params: Sequence[torch.Tensor],
+                         states: Sequence[dict], *, coef: Sequence[torch.Tensor], lr: float,
+                         betas: tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
+                         step: int) -> None:
+        """Second half of the clipped step for every logical rank; coef[k]: rank k's coefficient."""
+        h = _H.AdamW()
+        h.lr, (h.beta1, h.beta2), h.eps, h.weight_decay, h.step = lr, betas, eps, weight_decay, step
+        n = params[0].numel()
+        code = _dtype_code(params[0].dtype)
+        self._check_shards(params, gshards, n, code)
+        for k in range(self.world):
+            if coef[k].dtype != torch.float32 or coef[k].numel() != 1 or coef[k].device != self.devices[k]:
+                raise ValueError(f"rank {k}: coef must be a 1-element fp32 tensor on {self.devices[k]}")
+        for g in self.groups:
+            dev = self.devices[g[0]]
+            _H.XgmiComm.step_adamw_shard_local(
+                [self.comms[k] for k in g], [gshards[k].data_ptr() for k in g], [coef[k].data_ptr() for k in g],
+                [params[k].data_ptr() for k in g], n, code, torch.cuda.current_stream(dev).cuda_stream,
+                [(states[k]["master"].data_ptr(), states[k]["exp_avg"].data_ptr(), states[k]["exp_avg_sq"].data_ptr())
+                 for k in g], h)
 
     def barrier(self) -> None:
         for g in self.groups:

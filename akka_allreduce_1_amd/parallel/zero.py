@@ -33,6 +33,20 @@ overlap the rest of backward ("optimizer in backward"). Valid because a paramete
 AccumulateGrad hook fires after its autograd node has used it; parameters shared between
 layers (tied weights) must not be used with this mode. `comm_grid` sets the workgroup count
 of the fused launches (0 = engine default).
+
+`max_grad_norm=x` clips the mean gradient by its global L2 norm over all parameters and ranks
+before the update (the formula of `torch.nn.utils.clip_grad_norm_`: coef = min(1, x / (norm +
+1e-6))). `torch.nn.utils.clip_grad_norm_(model.parameters(), ...)` cannot do it here: `p.grad`
+is a view of the un-reduced flat gradient. Unfused: after the reduce-scatter every rank takes
+the sum of squares of its gradient shards, the per-rank sums are all-gathered and added in
+rank order, and `grad_shard` is scaled before the optimizer runs. Fused: the step is split
+where the norm has to be known (csrc/hip/xgmi_clip.hip) - per bucket one launch that
+reduce-scatters into an fp32 shard `gshard` and sums its squares (from the gradient hooks on
+the side stream when `overlap=True`), then the coefficient, then per bucket one launch that
+runs AdamW on `gshard * coef` and all-gathers the parameters. `last_grad_norm` /
+`last_clip_coef` are 0-d fp32 device tensors of the last step (an inf norm gives coef 0, a NaN
+norm NaN everywhere); reading them costs no sync. Not with `step_in_backward`: an update
+cannot precede a norm over gradients that do not exist yet.
 """
 from __future__ import annotations
 
@@ -40,7 +54,7 @@ from typing import Callable, Iterable
 
 import torch
 
-from .comm import comm_stream
+from .comm import clip_coef_from_records, comm_stream, gather_sq_records, sq_record
 
 _ALIGN_BYTES = 16
 
@@ -64,11 +78,15 @@ class ShardedDataParallel:
     def __init__(self, module: torch.nn.Module | Iterable[torch.nn.Parameter], comm,
                  optimizer_factory: Callable[[list[torch.nn.Parameter]], torch.optim.Optimizer] | None, *,
                  bucket_bytes: int = 64 << 20, overlap: bool = True, fused_adamw: dict | None = None,
-                 step_in_backward: bool = False, comm_grid: int = 0):
+                 step_in_backward: bool = False, comm_grid: int = 0, max_grad_norm: float | None = None):
         params = module.parameters() if isinstance(module, torch.nn.Module) else module
         self.params = [p for p in params if p.requires_grad]
         if not self.params:
             raise ValueError("no trainable parameters")
+        if max_grad_norm is not None and step_in_backward:
+            raise ValueError("max_grad_norm cannot be combined with step_in_backward: the update of a bucket "
+                             "would precede the norm over gradients that do not exist yet")
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.comm = comm
         self.world = int(getattr(comm, "world"))
         self.rank = int(getattr(comm, "rank"))
@@ -91,18 +109,27 @@ class ShardedDataParallel:
                 if b.numel * b.flat_param.element_size() > cap:
                     raise ValueError(f"fused_adamw: bucket of {b.numel} elements exceeds world * slot_bytes = {cap} B")
             self.adamw_states = [comm.adamw_state(b.flat_param) for b in self.buckets]
-            # without step_in_backward the fused launch runs in step(); with it, from the hooks
-            self.overlap = bool(step_in_backward) and self.on_gpu
+            # without step_in_backward the fused launch runs in step(); with it, from the hooks.
+            # Clipped: the reduce-scatter half may run from the hooks, the update half in step()
+            if self.max_grad_norm is None:
+                self.overlap = bool(step_in_backward) and self.on_gpu
+            else:
+                if not hasattr(comm, "step_adamw_shard"):
+                    raise ValueError("fused_adamw with max_grad_norm needs a communicator with step_adamw_shard")
+                self.gshards = [comm.gshard(b.flat_param) for b in self.buckets]  # scratch: not in state_dict()
+                self._sqs = [None] * len(self.buckets)
             self.optimizer = None
         else:
             if step_in_backward:
                 raise ValueError("step_in_backward needs fused_adamw")
             self.optimizer = optimizer_factory([b.shard_param for b in self.buckets])
-        self.step_in_backward = self.fused is not None and self.overlap
+        self.step_in_backward = self.fused is not None and self.overlap and self.max_grad_norm is None
+        self.last_grad_norm = torch.zeros((), dtype=torch.float32, device=self.device)
+        self.last_clip_coef = torch.ones((), dtype=torch.float32, device=self.device)
         self._t_started = False
         self._hooks = [p.register_post_accumulate_grad_hook(self._on_grad) for p in self.params]
         self._next = 0
-        self.stats = {"steps": 0, "reduce_scatter_bytes": 0, "all_gather_bytes": 0}
+        self.stats = {"steps": 0, "reduce_scatter_bytes": 0, "all_gather_bytes": 0, "clip_bytes": 0}
 
     # ------------------------------------------------------------------ layout
     def _build(self, bucket_bytes: int) -> list[_Bucket]:
@@ -170,9 +197,26 @@ class ShardedDataParallel:
         self.stats["reduce_scatter_bytes"] += b.flat_grad.numel() * b.flat_grad.element_size()
         self.stats["all_gather_bytes"] += b.flat_param.numel() * b.flat_param.element_size()
 
+    def _rs_sq_bucket(self, b: _Bucket) -> None:
+        """Clipped fused step, first half of a bucket: reduce-scatter into gshard + sum of squares."""
+        def launch():
+            self._sqs[b.index] = self.comm.reduce_scatter_sq(b.flat_grad, self.gshards[b.index], op="avg",
+                                                             grid=self.fused["grid"])
+        if self.overlap:
+            self.stream.wait_stream(torch.cuda.current_stream(self.device))
+            with torch.cuda.stream(self.stream):
+                launch()
+        else:
+            launch()
+        b.launched = True
+        self.stats["reduce_scatter_bytes"] += b.flat_grad.numel() * b.flat_grad.element_size()
+
     def _reduce(self, b: _Bucket) -> None:
         if self.fused is not None:
-            self._fused_bucket(b)
+            if self.max_grad_norm is not None:
+                self._rs_sq_bucket(b)
+            else:
+                self._fused_bucket(b)
             return
         if self.on_gpu:
             self.stream.wait_stream(torch.cuda.current_stream(self.device))
@@ -197,6 +241,22 @@ class ShardedDataParallel:
             self._t_started = False
             self.stats["steps"] += 1
             return
+        if self.fused is not None and self.max_grad_norm is not None:
+            self._launch_ready(all_=True)
+            if self.overlap:
+                torch.cuda.current_stream(self.device).wait_stream(self.stream)
+            self.last_grad_norm, self.last_clip_coef = self.comm.clip_coef(self._sqs, self.max_grad_norm)
+            self._t += 1
+            for b, st, gs in zip(self.buckets, self.adamw_states, self.gshards):
+                self.comm.step_adamw_shard(gs, b.flat_param, st, coef=self.last_clip_coef, step=self._t, **self.fused)
+                self.stats["all_gather_bytes"] += b.flat_param.numel() * b.flat_param.element_size()
+                self.stats["clip_bytes"] += 8 * gs.numel()  # the fp32 shard: written once, read once
+            for b in self.buckets:
+                b.pending = len(b.params)
+                b.launched = False
+            self._next = 0
+            self.stats["steps"] += 1
+            return
         if self.fused is not None:
             self._t += 1
             for b, st in zip(self.buckets, self.adamw_states):
@@ -210,6 +270,8 @@ class ShardedDataParallel:
         self._launch_ready(all_=True)
         if self.on_gpu:
             torch.cuda.current_stream(self.device).wait_stream(self.stream)
+        if self.max_grad_norm is not None:
+            self._clip_shards()
         self.optimizer.step()
         for b in self.buckets:
             # the shard is part of the gather's output buffer: gather from a copy
@@ -221,6 +283,15 @@ class ShardedDataParallel:
             b.launched = False
         self._next = 0
         self.stats["steps"] += 1
+
+    def _clip_shards(self) -> None:
+        """Unfused clipping: this rank's sum of squares over its gradient shards (fp32, bucket
+        order), the ranks' sums all-gathered and added in rank order, every shard scaled."""
+        sqs = [b.grad_shard.float().pow(2).sum() for b in self.buckets]
+        recs = gather_sq_records(self.comm, sq_record(sqs))
+        self.last_grad_norm, self.last_clip_coef = clip_coef_from_records(recs, self.max_grad_norm)
+        for b in self.buckets:
+            b.grad_shard.mul_(self.last_clip_coef)
 
     # ------------------------------------------------------------------ checkpoint / resume
     def state_dict(self) -> dict:
@@ -271,4 +342,6 @@ class ShardedDataParallel:
 
     def describe(self) -> list[dict]:
         return [{"bucket": b.index, "dtype": str(b.dtype), "params": len(b.params), "numel": b.numel,
-                 "shard": b.numel // self.world} for b in self.buckets]
+                 "shard": b.numel // self.world,
+                 "gshard_bytes": 4 * self.gshards[b.index].numel() if getattr(self, "gshards", None) else 0}
+                for b in self.buckets]

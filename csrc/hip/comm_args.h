@@ -156,6 +156,14 @@ struct CommArgs {
   uint64_t* split_dec;
   uint32_t* split_ctr;
   uint32_t* split_early;
+  // clipped step (xgmi_clip.hip), per rank. Both halves: the fp32 gradient shard (block_elems
+  // elements, block `rank`). Reduce-scatter half: one partial sum of squares per reduce unit
+  // (nch * sub floats of scratch) and where the rank's sum of squares goes. Update half: the
+  // clip coefficient (one fp32, read by every workgroup).
+  float* gshard[kMaxRanks];
+  float* sq_part[kMaxRanks];
+  float* sq_out[kMaxRanks];
+  const float* coef[kMaxRanks];
 };
 
 // A plane group's resident kernel (threshold_group_resident_kernel): y = 0 is the dispatcher
@@ -170,9 +178,9 @@ struct GroupResArgs {
 };
 static_assert(sizeof(CommArgs) + sizeof(GroupResArgs) <= 4096, "threshold_group_resident_kernel arguments exceed 4 KiB");
 // the kernels read these by offset: a reorder or a changed type must fail the build
-static_assert(sizeof(CommArgs) == 1248, "CommArgs is the kernel-argument ABI");
+static_assert(sizeof(CommArgs) == 1760, "CommArgs is the kernel-argument ABI");
 static_assert(offsetof(CommArgs, stamps) == 1136 && offsetof(CommArgs, oneshot) == 1216 &&
-                  offsetof(CommArgs, split_early) == 1240,
+                  offsetof(CommArgs, split_early) == 1240 && offsetof(CommArgs, gshard) == 1248,
               "CommArgs is the kernel-argument ABI");
 
 }  // namespace mxar

@@ -445,6 +445,8 @@ void bind_hip(py::module_& m) {
       .def_readonly("ll", &CommStats::ll)
       .def_readonly("coll", &CommStats::coll)
       .def_readonly("adamw", &CommStats::adamw)
+      .def_readonly("rs_sq", &CommStats::rs_sq)
+      .def_readonly("adamw_shard", &CommStats::adamw_shard)
       .def_readonly("stream_switches", &CommStats::stream_switches);
 
   py::class_<AdamW>(h, "AdamW")
@@ -689,6 +691,61 @@ void bind_hip(py::module_& m) {
           },
           py::arg("comms"), py::arg("grads"), py::arg("params"), py::arg("n"), py::arg("dtype"), py::arg("stream"),
           py::arg("states"), py::arg("hyper"), py::arg("scale") = 1.0f)
+      .def(
+          "reduce_scatter_sq",
+          [](XgmiComm& c, uintptr_t grads, uintptr_t gshard, uintptr_t sq, int64_t n, DType dt, uintptr_t stream,
+             float scale) {
+            py::gil_scoped_release r;
+            c.reduce_scatter_sq(as_cptr(grads), reinterpret_cast<float*>(gshard), reinterpret_cast<float*>(sq), n, dt,
+                                as_stream(stream), scale);
+          },
+          py::arg("grads"), py::arg("gshard"), py::arg("sq"), py::arg("n"), py::arg("dtype"), py::arg("stream"),
+          py::arg("scale") = 1.0f)
+      .def_static(
+          "reduce_scatter_sq_local",
+          [](const std::vector<XgmiComm*>& comms, const std::vector<uintptr_t>& grads,
+             const std::vector<uintptr_t>& gshards, const std::vector<uintptr_t>& sqs, int64_t n, DType dt,
+             uintptr_t stream, float scale) {
+            std::vector<const void*> g;
+            std::vector<float*> gs, sq;
+            for (auto x : grads) g.push_back(as_cptr(x));
+            for (auto x : gshards) gs.push_back(reinterpret_cast<float*>(x));
+            for (auto x : sqs) sq.push_back(reinterpret_cast<float*>(x));
+            py::gil_scoped_release r;
+            XgmiComm::reduce_scatter_sq_local(comms, g, gs, sq, n, dt, as_stream(stream), scale);
+          },
+          py::arg("comms"), py::arg("grads"), py::arg("gshards"), py::arg("sqs"), py::arg("n"), py::arg("dtype"),
+          py::arg("stream"), py::arg("scale") = 1.0f)
+      .def(
+          "step_adamw_shard",
+          [](XgmiComm& c, uintptr_t gshard, uintptr_t coef, uintptr_t params, int64_t n, DType dt, uintptr_t stream,
+             uintptr_t mp, uintptr_t m1, uintptr_t m2, const AdamW& hp) {
+            AdamShard st{reinterpret_cast<float*>(mp), reinterpret_cast<float*>(m1), reinterpret_cast<float*>(m2)};
+            py::gil_scoped_release r;
+            c.step_adamw_shard(reinterpret_cast<const float*>(gshard), reinterpret_cast<const float*>(coef),
+                               as_ptr(params), n, dt, as_stream(stream), st, hp);
+          },
+          py::arg("gshard"), py::arg("coef"), py::arg("params"), py::arg("n"), py::arg("dtype"), py::arg("stream"),
+          py::arg("master"), py::arg("exp_avg"), py::arg("exp_avg_sq"), py::arg("hyper"))
+      .def_static(
+          "step_adamw_shard_local",
+          [](const std::vector<XgmiComm*>& comms, const std::vector<uintptr_t>& gshards,
+             const std::vector<uintptr_t>& coefs, const std::vector<uintptr_t>& params, int64_t n, DType dt,
+             uintptr_t stream, const std::vector<std::tuple<uintptr_t, uintptr_t, uintptr_t>>& states,
+             const AdamW& hp) {
+            std::vector<const float*> gs, cf;
+            std::vector<void*> p;
+            std::vector<AdamShard> st;
+            for (auto x : gshards) gs.push_back(reinterpret_cast<const float*>(x));
+            for (auto x : coefs) cf.push_back(reinterpret_cast<const float*>(x));
+            for (auto x : params) p.push_back(as_ptr(x));
+            for (auto& [a, b, c] : states)
+              st.push_back({reinterpret_cast<float*>(a), reinterpret_cast<float*>(b), reinterpret_cast<float*>(c)});
+            py::gil_scoped_release r;
+            XgmiComm::step_adamw_shard_local(comms, gs, cf, p, n, dt, as_stream(stream), st, hp);
+          },
+          py::arg("comms"), py::arg("gshards"), py::arg("coefs"), py::arg("params"), py::arg("n"), py::arg("dtype"),
+          py::arg("stream"), py::arg("states"), py::arg("hyper"))
       .def("block_elems", &XgmiComm::block_elems, py::arg("n"), py::arg("dtype"))
       .def(
           "collective",

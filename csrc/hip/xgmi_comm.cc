@@ -155,6 +155,7 @@ XgmiComm::~XgmiComm() {
   for (int k = 0; k < static_cast<int>(probe_peers_.size()); ++k)
     if (k != rank_ && probe_peers_[k]) (void)hipIpcCloseMemHandle(probe_peers_[k]);
   if (probe_coarse_) (void)hipFree(probe_coarse_);
+  if (sq_part_) (void)hipFree(sq_part_);
   if (slab_ && own_slab_) (void)hipFree(slab_);
   if (ctl_ && own_ctl_) (void)hipFree(ctl_);
 }
@@ -352,6 +353,16 @@ static void set_geometry(CommArgs& a, const LaunchGeometry& g) {
   a.sgroup = g.sgroup;
 }
 
+static void set_adamw_hyper(CommArgs& a, const AdamW& h) {
+  a.lr = h.lr;
+  a.beta1 = h.beta1;
+  a.beta2 = h.beta2;
+  a.eps = h.eps;
+  a.wd = h.weight_decay;
+  a.c1 = 1.f - std::pow(h.beta1, static_cast<float>(h.step));
+  a.c2_sqrt = std::sqrt(1.f - std::pow(h.beta2, static_cast<float>(h.step)));
+}
+
 // One launch for the ranks `group` (all on one device, consecutive rank ids starting at
 // group[0]->rank()) over one segment of n elements.
 void XgmiComm::launch_segment(const std::vector<XgmiComm*>& group, const char* const* ins, char* const* outs,
@@ -385,13 +396,7 @@ void XgmiComm::launch_segment(const std::vector<XgmiComm*>& group, const char* c
       a.opt_m[y] = (*adam_state)[y].exp_avg;
       a.opt_v[y] = (*adam_state)[y].exp_avg_sq;
     }
-    a.lr = adam->lr;
-    a.beta1 = adam->beta1;
-    a.beta2 = adam->beta2;
-    a.eps = adam->eps;
-    a.wd = adam->weight_decay;
-    a.c1 = 1.f - std::pow(adam->beta1, static_cast<float>(adam->step));
-    a.c2_sqrt = std::sqrt(1.f - std::pow(adam->beta2, static_cast<float>(adam->step)));
+    set_adamw_hyper(a, *adam);
     launch_adamw(a, grid, stream, dt);
     hip_check(hipGetLastError(), "adamw launch");
     for (XgmiComm* c : group) {
@@ -523,6 +528,138 @@ void XgmiComm::step_adamw_local(const std::vector<XgmiComm*>& group, const std::
 void XgmiComm::step_adamw(const void* grads, void* params, int64_t n, DType dt, hipStream_t stream,
                           const AdamShard& st, const AdamW& h, float scale) {
   step_adamw_local({this}, {grads}, {params}, n, dt, stream, {st}, h, scale);
+}
+
+// ---------------------------------------------------------------------------------
+// The clipped step (xgmi_clip.hip): the fused step in two launches on its geometry
+// ---------------------------------------------------------------------------------
+static bool overlaps(const void* a, int64_t abytes, const void* b, int64_t bbytes) {
+  const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+  return x < y + static_cast<uintptr_t>(bbytes) && y < x + static_cast<uintptr_t>(abytes);
+}
+
+CommArgs XgmiComm::clip_args(const std::vector<XgmiComm*>& group, int64_t n, DType dt, const char* what,
+                             hipStream_t stream, dim3* grid) {
+  const XgmiComm& c0 = *group[0];
+  const int64_t es = static_cast<int64_t>(dtype_size(dt));
+  for (size_t y = 0; y < group.size(); ++y) {
+    const XgmiComm& c = *group[y];
+    if (!c.connected_) throw std::runtime_error("XgmiComm: connect() first");
+    if (c.device_ != c0.device_ || c.rank_ != c0.rank_ + static_cast<int>(y) || c.world_ != c0.world_)
+      throw std::invalid_argument("XgmiComm: a grouped launch needs consecutive ranks on one device");
+  }
+  if (n * es > c0.world_ * c0.slot_bytes_)
+    throw std::invalid_argument(std::string(what) + ": tensor exceeds one launch (n * dtype <= world * slot_bytes)");
+  hip_check(hipSetDevice(c0.device_), "hipSetDevice");
+  for (XgmiComm* c : group) {
+    ++c->stats_.calls;
+    c->stats_.bytes += n * es;
+  }
+  order_group(group, stream);
+  const int ranks_here = static_cast<int>(group.size());
+  const LaunchGeometry g = plan_allreduce(Algo::TwoShot, c0.knobs(), n, es, ranks_here, true);
+  CommArgs a = c0.base_args(group);
+  a.n = n;
+  set_geometry(a, g);
+  *grid = dim3(g.gx, ranks_here);
+  return a;
+}
+
+void XgmiComm::reduce_scatter_sq_local(const std::vector<XgmiComm*>& group, const std::vector<const void*>& grads,
+                                       const std::vector<float*>& gshards, const std::vector<float*>& sqs, int64_t n,
+                                       DType dt, hipStream_t stream, float scale) {
+  if (group.empty() || grads.size() != group.size() || gshards.size() != group.size() || sqs.size() != group.size())
+    throw std::invalid_argument("reduce_scatter_sq: one grads / gshard / sq per rank");
+  const int64_t es = static_cast<int64_t>(dtype_size(dt));
+  const int64_t shard_bytes = group[0]->block_elems(n, dt) * 4;
+  for (size_t y = 0; y < group.size(); ++y) {
+    if ((reinterpret_cast<uintptr_t>(grads[y]) | reinterpret_cast<uintptr_t>(gshards[y])) & 15)
+      throw std::invalid_argument("reduce_scatter_sq: buffers must be 16-byte aligned");
+    if (sqs[y] == nullptr || (reinterpret_cast<uintptr_t>(sqs[y]) & 3))
+      throw std::invalid_argument("reduce_scatter_sq: sq must be a 4-byte aligned fp32");
+    if (overlaps(grads[y], n * es, gshards[y], shard_bytes) || overlaps(sqs[y], 4, gshards[y], shard_bytes) ||
+        overlaps(sqs[y], 4, grads[y], n * es))
+      throw std::invalid_argument("reduce_scatter_sq: grads, gshard and sq must not overlap");
+  }
+  if (n <= 0) return;
+  dim3 grid;
+  CommArgs a = clip_args(group, n, dt, "reduce_scatter_sq", stream, &grid);
+  TraceScope span("xgmi", [&] {
+    return std::make_pair("rs_sq " + std::to_string(n * es) + "B", "{\"rank\":" + std::to_string(group[0]->rank_) + "}");
+  });
+  for (size_t y = 0; y < group.size(); ++y) {
+    XgmiComm& c = *group[y];
+    if (c.sq_part_ == nullptr)  // one partial per reduce unit: nch * sub <= maxch (plan_twoshot)
+      hip_check(hipMalloc(&c.sq_part_, static_cast<size_t>(c.maxch_) * sizeof(float)), "hipMalloc(sq partials)");
+    a.in[y] = static_cast<const char*>(grads[y]);
+    a.gshard[y] = gshards[y];
+    a.sq_part[y] = c.sq_part_;
+    a.sq_out[y] = sqs[y];
+  }
+  a.scale = scale;
+  launch_rs_sq(a, grid, stream, dt);
+  hip_check(hipGetLastError(), "rs_sq launch");
+  for (XgmiComm* c : group) {
+    ++c->stats_.launches;
+    ++c->stats_.rs_sq;
+  }
+}
+
+void XgmiComm::reduce_scatter_sq(const void* grads, float* gshard, float* sq, int64_t n, DType dt, hipStream_t stream,
+                                 float scale) {
+  reduce_scatter_sq_local({this}, {grads}, {gshard}, {sq}, n, dt, stream, scale);
+}
+
+void XgmiComm::step_adamw_shard_local(const std::vector<XgmiComm*>& group, const std::vector<const float*>& gshards,
+                                      const std::vector<const float*>& coefs, const std::vector<void*>& params,
+                                      int64_t n, DType dt, hipStream_t stream, const std::vector<AdamShard>& st,
+                                      const AdamW& h) {
+  if (group.empty() || gshards.size() != group.size() || coefs.size() != group.size() ||
+      params.size() != group.size() || st.size() != group.size())
+    throw std::invalid_argument("step_adamw_shard: one gshard / coef / params / shard state per rank");
+  const int64_t es = static_cast<int64_t>(dtype_size(dt));
+  const int64_t shard_bytes = group[0]->block_elems(n, dt) * 4;
+  for (size_t y = 0; y < group.size(); ++y) {
+    if ((reinterpret_cast<uintptr_t>(gshards[y]) | reinterpret_cast<uintptr_t>(params[y]) |
+         reinterpret_cast<uintptr_t>(st[y].param) | reinterpret_cast<uintptr_t>(st[y].exp_avg) |
+         reinterpret_cast<uintptr_t>(st[y].exp_avg_sq)) & 15)
+      throw std::invalid_argument("step_adamw_shard: buffers must be 16-byte aligned");
+    if (coefs[y] == nullptr || (reinterpret_cast<uintptr_t>(coefs[y]) & 3))
+      throw std::invalid_argument("step_adamw_shard: coef must be a 4-byte aligned fp32");
+    if (overlaps(gshards[y], shard_bytes, params[y], n * es) || overlaps(coefs[y], 4, params[y], n * es))
+      throw std::invalid_argument("step_adamw_shard: gshard, coef and params must not overlap");
+    for (const float* s : {st[y].param, st[y].exp_avg, st[y].exp_avg_sq})
+      if (overlaps(s, shard_bytes, gshards[y], shard_bytes) || overlaps(s, shard_bytes, coefs[y], 4))
+        throw std::invalid_argument("step_adamw_shard: the shard state must not overlap gshard or coef");
+  }
+  if (n <= 0) return;
+  if (h.step < 1) throw std::invalid_argument("step_adamw_shard: step counts from 1");
+  dim3 grid;
+  CommArgs a = clip_args(group, n, dt, "step_adamw_shard", stream, &grid);
+  TraceScope span("xgmi", [&] {
+    return std::make_pair("adamw_shard " + std::to_string(n * es) + "B",
+                          "{\"rank\":" + std::to_string(group[0]->rank_) + "}");
+  });
+  for (size_t y = 0; y < group.size(); ++y) {
+    a.gshard[y] = const_cast<float*>(gshards[y]);
+    a.coef[y] = coefs[y];
+    a.out[y] = static_cast<char*>(params[y]);
+    a.opt_p[y] = st[y].param;
+    a.opt_m[y] = st[y].exp_avg;
+    a.opt_v[y] = st[y].exp_avg_sq;
+  }
+  set_adamw_hyper(a, h);
+  launch_adamw_shard(a, grid, stream, dt);
+  hip_check(hipGetLastError(), "adamw_shard launch");
+  for (XgmiComm* c : group) {
+    ++c->stats_.launches;
+    ++c->stats_.adamw_shard;
+  }
+}
+
+void XgmiComm::step_adamw_shard(const float* gshard, const float* coef, void* params, int64_t n, DType dt,
+                                hipStream_t stream, const AdamShard& st, const AdamW& h) {
+  step_adamw_shard_local({this}, {gshard}, {coef}, {params}, n, dt, stream, {st}, h);
 }
 
 void XgmiComm::allreduce(const void* in, void* out, int64_t n, DType dt, hipStream_t stream, Algo algo, float scale) {

@@ -52,6 +52,8 @@ struct AdamShard {
 struct CommStats {
   uint64_t calls = 0, launches = 0, bytes = 0, oneshot = 0, twoshot = 0, ring = 0, threshold = 0, ll = 0, coll = 0,
            adamw = 0, stream_switches = 0;
+  // the clipped step's halves (xgmi_clip.hip): they count here, not in `adamw` or `coll`
+  uint64_t rs_sq = 0, adamw_shard = 0;
 };
 
 class XgmiComm {
@@ -247,6 +249,26 @@ class XgmiComm {
                                const std::vector<AdamShard>& st, const AdamW& h, float scale);
   int64_t block_elems(int64_t n, DType dt) const;
 
+  // The clipped step (xgmi_clip.hip): the fused step split where the global gradient norm has
+  // to be known, two launches on the fused step's geometry and limits.
+  // reduce_scatter_sq: grads [n] of every rank are reduce-scattered (x scale, fp32, rank order)
+  // into gshard (fp32, block_elems(n) elements, block `rank`; nothing past the valid length is
+  // written) and *sq = the sum of the squares of this rank's shard (device fp32; fixed summation
+  // tree, see the kernel file). The gradients are not written.
+  void reduce_scatter_sq(const void* grads, float* gshard, float* sq, int64_t n, DType dt, hipStream_t stream,
+                         float scale);
+  static void reduce_scatter_sq_local(const std::vector<XgmiComm*>& comms, const std::vector<const void*>& grads,
+                                      const std::vector<float*>& gshards, const std::vector<float*>& sqs, int64_t n,
+                                      DType dt, hipStream_t stream, float scale);
+  // step_adamw_shard: AdamW on the shard state with gshard[i] * *coef as the gradient (coef: a
+  // device fp32), the updated parameters all-gathered into `params` [n] as step_adamw does.
+  void step_adamw_shard(const float* gshard, const float* coef, void* params, int64_t n, DType dt,
+                        hipStream_t stream, const AdamShard& st, const AdamW& h);
+  static void step_adamw_shard_local(const std::vector<XgmiComm*>& comms, const std::vector<const float*>& gshards,
+                                     const std::vector<const float*>& coefs, const std::vector<void*>& params,
+                                     int64_t n, DType dt, hipStream_t stream, const std::vector<AdamShard>& st,
+                                     const AdamW& h);
+
   // Collectives on [P][m] buffers (m elements per block, m * dtype a multiple of 16 B):
   //   AllToAll      in[P][m] -> out[P][m]   out_r[s] = in_s[r]
   //   AllGather     in[m]    -> out[P][m]   out_r[s] = in_s
@@ -355,6 +377,9 @@ class XgmiComm {
   static void run_rooted(const std::vector<XgmiComm*>& group, Rooted kind, const std::vector<const void*>& ins,
                          const std::vector<void*>& outs, int64_t n, DType dt, int root, hipStream_t stream,
                          float scale);
+  // The clipped step's halves: group checks, stats, stream order and the `adamw` geometry
+  static CommArgs clip_args(const std::vector<XgmiComm*>& group, int64_t n, DType dt, const char* what,
+                            hipStream_t stream, dim3* grid);
   // The fields every launch of `group` shares: membership, slab layout, timeout, fence, peers.
   CommArgs base_args(const std::vector<XgmiComm*>& group) const;
   // A grouped launch: connected, consecutive ranks on one device (need_rows: and one lag ring
@@ -371,6 +396,7 @@ class XgmiComm {
                             float thc, int32_t* counts, float scale, bool rescale, const RoundSpec* spec = nullptr);
 
   int rank_, world_, device_, grid_, rows_;
+  float* sq_part_ = nullptr;  // reduce_scatter_sq: maxch partial sums of squares (allocated at the first call)
   char* probe_coarse_ = nullptr;  // this rank's coarse-grained probe buffer (xgmi_probe.hip)
   std::vector<char*> probe_peers_;  // the peers' coarse probe buffers, IPC-mapped
   int64_t slot_bytes_, slot_stride_, maxch_, off_S_, off_R_, off_B_, slab_bytes_;

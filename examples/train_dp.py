@@ -88,6 +88,8 @@ def main() -> int:
     ap.add_argument("--cpu", action="store_true", help="gloo on the CPU (TorchDistComm)")
     ap.add_argument("--overlap", choices=["on", "off", "auto"], default="on",
                     help="buckets beside backward, after it, or measured in the first steps (GPU)")
+    ap.add_argument("--max-grad-norm", type=float, default=None,
+                    help="clip the mean gradient by its global L2 norm before the optimizer step")
     args = ap.parse_args()
 
     rank, world, local = init_distributed("gloo" if args.cpu else "nccl")
@@ -111,6 +113,8 @@ def main() -> int:
         loss = F.cross_entropy(model(x).flatten(0, 1), y.flatten())
         loss.backward()          # the reducer's hooks launch full buckets during backward
         reducer.wait()           # the mean gradient is in every .grad
+        if args.max_grad_norm is not None:  # after the allreduce stock torch clips the mean gradient
+            torch.nn.utils.clip_grad_norm_(model.parameters(), args.max_grad_norm)
         opt.step()
         reducer.zero_grad()      # keep .grad as views of the buckets
         lv = float(loss.detach())

@@ -1,0 +1,143 @@
+#!/usr/bin/env python3
+"""What gradient clipping costs the fused sharded-DP step: P logical ranks on ONE MI355X, n
+parameters in one bucket (default 8 ranks x 134 M bf16, the size of profiles/round4).
+
+Three step times, alternating in one call:
+  clipped   reduce_scatter_sq + clip_coef + step_adamw_shard of this tree
+  fused     step_adamw of this tree
+  parent    step_adamw of another checkout (--parent PATH, built there), in child processes
+            started between this tree's rounds
+
+Every round times `iters` steps of each variant in turn with device events; the figure of a
+variant is the median over rounds of the round's median. Byte model per owned parameter: fused
+14 B read + 14 B written, clipped 8 B more (the fp32 shard written and read once).
+
+    python tools/clip_step_cost.py --parent ab_old --out profiles/clip_step.json
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HP = dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01)
+
+
+def _timed(fn, iters):
+    import torch
+
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
+    for a, b in ev:
+        a.record()
+        fn()
+        b.record()
+    torch.cuda.synchronize()
+    return statistics.median(a.elapsed_time(b) for a, b in ev)
+
+
+def measure(args, variants):
+    """Round medians (ms) of the variants, alternating, in this process with the package that is
+    first on sys.path."""
+    import torch
+
+    from akka_allreduce_1_amd.ops import dtype_code, fill_uniform
+    from akka_allreduce_1_amd.parallel import LocalCluster
+
+    dev = torch.device("cuda", 0)
+    P, n = args.ranks, args.n
+    dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
+    es = 2 if dtype == torch.bfloat16 else 4
+    per_rank = -(-n * es // P)
+    slot = (per_rank + (1 << 20) - 1) // (1 << 20) * (1 << 20)  # one block per slot, whole MiB
+    cl = LocalCluster(P, slot_bytes=slot, grid=args.grid, timeout_s=20)
+    b = cl.comms[0].block_elems(n, dtype_code(dtype))
+    grads = [fill_uniform(torch.empty(n, dtype=dtype, device=dev), seed=10 + k) for k in range(P)]
+    params = [fill_uniform(torch.empty(n, dtype=dtype, device=dev), seed=1) for _ in range(P)]
+    states = [{k: torch.zeros(b, device=dev) for k in ("master", "exp_avg", "exp_avg_sq")} for _ in range(P)]
+    gshards = [torch.zeros(b, device=dev) for _ in range(P)] if "clipped" in variants else None
+    step = [0]
+
+    def fused():
+        step[0] += 1
+        cl.step_adamw(grads, params, states, step=step[0], **HP)
+
+    def clipped():
+        step[0] += 1
+        sqs = cl.reduce_scatter_sq(grads, gshards)
+        _, coef = cl.clip_coef(sqs, 1.0)
+        cl.step_adamw_shard(gshards, params, states, coef=coef, step=step[0], **HP)
+
+    fns = {"fused": fused, "clipped": clipped}
+    for v in variants:
+        for _ in range(args.warmup):
+            fns[v]()
+    cl.check()
+    out = {v: [] for v in variants}
+    for _ in range(args.rounds):
+        for v in variants:
+            out[v].append(_timed(fns[v], args.iters))
+    cl.check()
+    return out
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--ranks", type=int, default=8)
+    ap.add_argument("--n", type=int, default=134_217_728)
+    ap.add_argument("--dtype", choices=["bf16", "fp32"], default="bf16")
+    ap.add_argument("--grid", type=int, default=512)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--parent", default=None, help="another built checkout whose fused step is timed too")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.child:  # the fused step of the checkout on PYTHONPATH, one round set
+        print(json.dumps(measure(args, ["fused"])), flush=True)
+        return 0
+    res = {"clipped": [], "fused": [], "parent": []}
+    passes = 3 if args.parent else 1
+    for _ in range(passes):  # this tree and the parent take turns
+        here = measure(args, ["clipped", "fused"])
+        res["clipped"] += here["clipped"]
+        res["fused"] += here["fused"]
+        if args.parent:
+            tree = os.path.abspath(args.parent)
+            cmd = [sys.executable, os.path.join(tree, "tools", "clip_step_cost.py")]
+            if not os.path.exists(cmd[1]):  # the parent has no such tool: this file, its package
+                cmd = [sys.executable, os.path.abspath(__file__)]
+            cmd += ["--child", "--ranks", str(args.ranks), "--n", str(args.n), "--dtype", args.dtype, "--grid",
+                    str(args.grid), "--iters", str(args.iters), "--warmup", str(args.warmup), "--rounds",
+                    str(args.rounds)]
+            r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=tree,
+                               env=dict(os.environ, PYTHONPATH=tree, MXAR_CLIP_COST_TREE=tree))
+            if r.returncode != 0:
+                print(r.stderr[-2000:], file=sys.stderr)
+                return 1
+            res["parent"] += json.loads(r.stdout.strip().splitlines()[-1])["fused"]
+    med = {k: round(statistics.median(v), 4) for k, v in res.items() if v}
+    es = 2 if args.dtype == "bf16" else 4
+    owned = args.n  # all ranks live on this device: every parameter is owned here once
+    summary = {"ranks": args.ranks, "n": args.n, "dtype": args.dtype, "grid": args.grid, "median_ms": med,
+               "rounds_ms": {k: [round(x, 4) for x in v] for k, v in res.items() if v},
+               "clipped_over_fused": round(med["clipped"] / med["fused"], 4),
+               "byte_model": {"fused_B_per_param": 28, "clipped_B_per_param": 36, "ratio": round(36 / 28, 4),
+                              "elem_size": es, "owned_params_on_device": owned}}
+    print(json.dumps(summary), flush=True)
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(summary, f, indent=1)
+    return 0
+
+
+if __name__ == "__main__":
+    if os.environ.get("MXAR_CLIP_COST_TREE"):  # a child: import the package of that checkout
+        sys.path.insert(0, os.environ["MXAR_CLIP_COST_TREE"])
+    else:
+        sys.path.insert(0, ROOT)
+    sys.exit(main())
