@@ -667,11 +667,14 @@ class XgmiCommunicator:
         return torch.zeros(self.shard_len(params.numel(), params.dtype), dtype=torch.float32, device=self.device)
 
     def reduce_scatter_sq(self, grads: torch.Tensor, gshard: torch.Tensor, *, op: str = "avg",
-                          grid: int = 0) -> torch.Tensor:
+                          grid: int = 0, accumulate: bool = False) -> torch.Tensor:
         """First half of the clipped step, one launch: reduce-scatter `grads` (mean by default;
         fp32, rank order) into `gshard` (fp32, `shard_len(n)` elements, block `rank`) and return
         the sum of the squares of this rank's shard as a device fp32 scalar (fixed summation
-        tree: the same bits whatever order the workgroups arrive in). `grads` is not written."""
+        tree: the same bits whatever order the workgroups arrive in). `grads` is not written.
+        `accumulate=True` adds into `gshard` instead (gradient accumulation: gshard[i] =
+        fl32(gshard[i] + fl32(scale * sum)), two roundings as plain fp32 torch ops give) and
+        returns the sum of the squares of the new values."""
         if op not in ("sum", "avg"):
             raise ValueError(f"unsupported op {op!r}")
         if gshard.dtype != torch.float32 or gshard.numel() != self.shard_len(grads.numel(), grads.dtype):
@@ -682,7 +685,7 @@ class XgmiCommunicator:
         sq = torch.zeros(1, dtype=torch.float32, device=self.device)
         self._c.reduce_scatter_sq(grads.data_ptr(), gshard.data_ptr(), sq.data_ptr(), grads.numel(),
                                   _dtype_code(grads.dtype), _current_stream(self._dev),
-                                  1.0 / self.world if op == "avg" else 1.0)
+                                  1.0 / self.world if op == "avg" else 1.0, bool(accumulate))
         return sq
 
     def clip_coef(self, sqs, max_norm: float) -> tuple[torch.Tensor, torch.Tensor]:
@@ -979,9 +982,10 @@ class LocalCluster:
                  for k in g], h, 1.0 / self.world if op == "avg" else 1.0)
 
     def reduce_scatter_sq(self, grads: Sequence[torch.Tensor], gshards: Sequence[torch.Tensor], *,
-                          op: str = "avg") -> list[torch.Tensor]:
+                          op: str = "avg", accumulate: bool = False) -> list[torch.Tensor]:
         """First half of the clipped step for every logical rank (xgmi_clip.hip); returns the
-        ranks' sums of squares, one device fp32 scalar each."""
+        ranks' sums of squares, one device fp32 scalar each. `accumulate=True`: add into the
+        gshards (see XgmiCommunicator.reduce_scatter_sq)."""
         n = grads[0].numel()
         code = _dtype_code(grads[0].dtype)
         self._check_shards(grads, gshards, n, code)
@@ -991,7 +995,7 @@ class LocalCluster:
             _H.XgmiComm.reduce_scatter_sq_local(
                 [self.comms[k] for k in g], [grads[k].data_ptr() for k in g], [gshards[k].data_ptr() for k in g],
                 [sqs[k].data_ptr() for k in g], n, code, torch.cuda.current_stream(dev).cuda_stream,
-                1.0 / self.world if op == "avg" else 1.0)
+                1.0 / self.world if op == "avg" else 1.0, bool(accumulate))
         return sqs
 
     def _check_shards(self, full, gshards, n: int, code) -> None:

@@ -47,6 +47,24 @@ runs AdamW on `gshard * coef` and all-gathers the parameters. `last_grad_norm` /
 `last_clip_coef` are 0-d fp32 device tensors of the last step (an inf norm gives coef 0, a NaN
 norm NaN everywhere); reading them costs no sync. Not with `step_in_backward`: an update
 cannot precede a norm over gradients that do not exist yet.
+
+`grad_accumulation=True` runs one optimizer step over several micro-batches: call
+`accumulate()` after the backward of every micro-batch but the last and `step()` after the last.
+The optimizer sees the SUM over micro-batches of the rank-mean gradient (torch's convention:
+divide the loss by the number of micro-batches for a mean). torch's recipes (`no_sync()`, or a
+second `backward()` before `step()`) do not apply: `p.grad` is a view of the un-reduced flat
+gradient, a 16-bit one would be rounded at every micro-batch, and the bucket hooks launch a
+bucket once until they are re-armed. Here every micro-batch is reduce-scattered when its backward ends and summed in fp32 on the
+owned 1/P of the parameters (4 B per owned parameter), never in 16 bits. Fused: the accumulator
+is `gshard`; the reduce-scatter half of csrc/hip/xgmi_clip.hip overwrites it for the first
+micro-batch and adds into it after that (gshard = fl32(gshard + fl32(scale * sum)): the product
+rounded before the add, no fma, so plain fp32 torch ops reproduce it), then - once per step -
+the coefficient (a constant 1.0f when not clipping) and the update half. A step without
+`accumulate()` runs exactly the launches it runs without the flag. Unfused: one fp32
+accumulator per bucket the size of `grad_shard`; at `step()` `grad_shard` receives (sum * coef)
+rounded once. Norm and coefficient are those of the accumulated gradient. `accumulate()` zeroes
+the flat gradients itself; `zero_grad()` stays a between-steps call. Accumulators are scratch:
+`state_dict()` raises between `accumulate()` and `step()`. Not with `step_in_backward`.
 """
 from __future__ import annotations
 
@@ -78,11 +96,17 @@ class ShardedDataParallel:
     def __init__(self, module: torch.nn.Module | Iterable[torch.nn.Parameter], comm,
                  optimizer_factory: Callable[[list[torch.nn.Parameter]], torch.optim.Optimizer] | None, *,
                  bucket_bytes: int = 64 << 20, overlap: bool = True, fused_adamw: dict | None = None,
-                 step_in_backward: bool = False, comm_grid: int = 0, max_grad_norm: float | None = None):
+                 step_in_backward: bool = False, comm_grid: int = 0, max_grad_norm: float | None = None,
+                 grad_accumulation: bool = False):
         params = module.parameters() if isinstance(module, torch.nn.Module) else module
         self.params = [p for p in params if p.requires_grad]
         if not self.params:
             raise ValueError("no trainable parameters")
+        if grad_accumulation and step_in_backward:
+            raise ValueError("grad_accumulation cannot be combined with step_in_backward: the update of a bucket "
+                             "would precede the gradients of the later micro-batches")
+        self.grad_accumulation = bool(grad_accumulation)
+        self.micro_batches = 0  # accumulate() calls since the last step()
         if max_grad_norm is not None and step_in_backward:
             raise ValueError("max_grad_norm cannot be combined with step_in_backward: the update of a bucket "
                              "would precede the norm over gradients that do not exist yet")
@@ -113,16 +137,22 @@ class ShardedDataParallel:
             # Clipped: the reduce-scatter half may run from the hooks, the update half in step()
             if self.max_grad_norm is None:
                 self.overlap = bool(step_in_backward) and self.on_gpu
-            else:
+            if self.max_grad_norm is not None or self.grad_accumulation:
                 if not hasattr(comm, "step_adamw_shard"):
-                    raise ValueError("fused_adamw with max_grad_norm needs a communicator with step_adamw_shard")
-                self.gshards = [comm.gshard(b.flat_param) for b in self.buckets]  # scratch: not in state_dict()
+                    raise ValueError("fused_adamw with max_grad_norm or grad_accumulation needs a communicator "
+                                     "with step_adamw_shard")
+                # scratch, not in state_dict(): the fp32 gradient shard, also the accumulator over micro-batches
+                self.gshards = [comm.gshard(b.flat_param) for b in self.buckets]
                 self._sqs = [None] * len(self.buckets)
+                self._one = torch.ones(1, dtype=torch.float32, device=self.device)  # coef of an unclipped step
             self.optimizer = None
         else:
             if step_in_backward:
                 raise ValueError("step_in_backward needs fused_adamw")
             self.optimizer = optimizer_factory([b.shard_param for b in self.buckets])
+            if self.grad_accumulation:  # scratch, not in state_dict(): fp32 sums over micro-batches
+                self._accs = [torch.zeros(b.grad_shard.numel(), dtype=torch.float32, device=self.device)
+                              for b in self.buckets]
         self.step_in_backward = self.fused is not None and self.overlap and self.max_grad_norm is None
         self.last_grad_norm = torch.zeros((), dtype=torch.float32, device=self.device)
         self.last_clip_coef = torch.ones((), dtype=torch.float32, device=self.device)
@@ -130,6 +160,8 @@ class ShardedDataParallel:
         self._hooks = [p.register_post_accumulate_grad_hook(self._on_grad) for p in self.params]
         self._next = 0
         self.stats = {"steps": 0, "reduce_scatter_bytes": 0, "all_gather_bytes": 0, "clip_bytes": 0}
+        if self.grad_accumulation:
+            self.stats["accumulates"] = 0
 
     # ------------------------------------------------------------------ layout
     def _build(self, bucket_bytes: int) -> list[_Bucket]:
@@ -198,10 +230,13 @@ class ShardedDataParallel:
         self.stats["all_gather_bytes"] += b.flat_param.numel() * b.flat_param.element_size()
 
     def _rs_sq_bucket(self, b: _Bucket) -> None:
-        """Clipped fused step, first half of a bucket: reduce-scatter into gshard + sum of squares."""
+        """Split fused step, first half of a bucket: reduce-scatter into gshard + sum of squares.
+        The first micro-batch of a step overwrites gshard, later ones add into it."""
+        acc = self.micro_batches > 0
+
         def launch():
             self._sqs[b.index] = self.comm.reduce_scatter_sq(b.flat_grad, self.gshards[b.index], op="avg",
-                                                             grid=self.fused["grid"])
+                                                             grid=self.fused["grid"], accumulate=acc)
         if self.overlap:
             self.stream.wait_stream(torch.cuda.current_stream(self.device))
             with torch.cuda.stream(self.stream):
@@ -210,10 +245,13 @@ class ShardedDataParallel:
             launch()
         b.launched = True
         self.stats["reduce_scatter_bytes"] += b.flat_grad.numel() * b.flat_grad.element_size()
+        if acc:
+            self.stats["clip_bytes"] += 4 * self.gshards[b.index].numel()  # the old sum, read back
 
     def _reduce(self, b: _Bucket) -> None:
         if self.fused is not None:
-            if self.max_grad_norm is not None:
+            # grad_accumulation, unclipped: only accumulate() and a step() that follows one get here
+            if self.max_grad_norm is not None or self.grad_accumulation:
                 self._rs_sq_bucket(b)
             else:
                 self._fused_bucket(b)
@@ -234,27 +272,27 @@ class ShardedDataParallel:
         if self.step_in_backward:
             self._launch_ready(all_=True)  # buckets whose parameters got no gradient
             torch.cuda.current_stream(self.device).wait_stream(self.stream)
-            for b in self.buckets:
-                b.pending = len(b.params)
-                b.launched = False
-            self._next = 0
+            self._rearm()
             self._t_started = False
             self.stats["steps"] += 1
             return
-        if self.fused is not None and self.max_grad_norm is not None:
+        if self.fused is not None and (self.max_grad_norm is not None or self.micro_batches > 0):
+            # the split step: clipped, or the last micro-batch of an accumulated step
             self._launch_ready(all_=True)
             if self.overlap:
                 torch.cuda.current_stream(self.device).wait_stream(self.stream)
-            self.last_grad_norm, self.last_clip_coef = self.comm.clip_coef(self._sqs, self.max_grad_norm)
+            if self.max_grad_norm is not None:
+                self.last_grad_norm, self.last_clip_coef = self.comm.clip_coef(self._sqs, self.max_grad_norm)
+                coef = self.last_clip_coef
+            else:
+                coef = self._one
             self._t += 1
             for b, st, gs in zip(self.buckets, self.adamw_states, self.gshards):
-                self.comm.step_adamw_shard(gs, b.flat_param, st, coef=self.last_clip_coef, step=self._t, **self.fused)
+                self.comm.step_adamw_shard(gs, b.flat_param, st, coef=coef, step=self._t, **self.fused)
                 self.stats["all_gather_bytes"] += b.flat_param.numel() * b.flat_param.element_size()
                 self.stats["clip_bytes"] += 8 * gs.numel()  # the fp32 shard: written once, read once
-            for b in self.buckets:
-                b.pending = len(b.params)
-                b.launched = False
-            self._next = 0
+            self._rearm()
+            self.micro_batches = 0
             self.stats["steps"] += 1
             return
         if self.fused is not None:
@@ -263,35 +301,77 @@ class ShardedDataParallel:
                 self.comm.step_adamw(b.flat_grad, b.flat_param, st, step=self._t, **self.fused)
                 self.stats["reduce_scatter_bytes"] += b.flat_grad.numel() * b.flat_grad.element_size()
                 self.stats["all_gather_bytes"] += b.flat_param.numel() * b.flat_param.element_size()
-            for b in self.buckets:
-                b.pending = len(b.params)
+            self._rearm()
             self.stats["steps"] += 1
             return
         self._launch_ready(all_=True)
         if self.on_gpu:
             torch.cuda.current_stream(self.device).wait_stream(self.stream)
+        if self.micro_batches > 0:
+            self._add_shards()
         if self.max_grad_norm is not None:
             self._clip_shards()
+        elif self.micro_batches > 0:
+            for b, acc in zip(self.buckets, self._accs):
+                b.grad_shard.copy_(acc)
         self.optimizer.step()
         for b in self.buckets:
             # the shard is part of the gather's output buffer: gather from a copy
             src = b.shard_param.detach().clone()
             self.comm.all_gather(src, b.flat_param)
             self.stats["all_gather_bytes"] += b.flat_param.numel() * b.flat_param.element_size()
+        self._rearm()
+        self.micro_batches = 0
+        self.stats["steps"] += 1
+
+    def _rearm(self) -> None:
         for b in self.buckets:
             b.pending = len(b.params)
             b.launched = False
         self._next = 0
-        self.stats["steps"] += 1
+
+    def accumulate(self) -> None:
+        """End a micro-batch that is not the last of its optimizer step (call after its backward;
+        `step()` ends the last): finish this backward's reduce-scatters - buckets that got no
+        gradient included - into the fp32 accumulators (the first micro-batch of a step
+        overwrites them, later ones add), zero the flat gradients (stream-ordered after the
+        launches that read them: `zero_grad()` stays a between-steps call) and re-arm the
+        gradient hooks. Needs `grad_accumulation=True`."""
+        if not self.grad_accumulation:
+            raise RuntimeError("accumulate() needs ShardedDataParallel(..., grad_accumulation=True)")
+        self._launch_ready(all_=True)
+        if self.on_gpu:
+            torch.cuda.current_stream(self.device).wait_stream(self.stream)
+        if self.fused is None:
+            self._add_shards()
+        for b in self.buckets:
+            b.flat_grad.zero_()
+        self._rearm()
+        self.micro_batches += 1
+        self.stats["accumulates"] += 1
+
+    def _add_shards(self) -> None:
+        """Unfused accumulation: this micro-batch's reduce-scattered shard into the fp32 sum."""
+        for b, acc in zip(self.buckets, self._accs):
+            if self.micro_batches == 0:
+                acc.copy_(b.grad_shard)
+            else:
+                acc.add_(b.grad_shard.float())
 
     def _clip_shards(self) -> None:
         """Unfused clipping: this rank's sum of squares over its gradient shards (fp32, bucket
-        order), the ranks' sums all-gathered and added in rank order, every shard scaled."""
-        sqs = [b.grad_shard.float().pow(2).sum() for b in self.buckets]
+        order), the ranks' sums all-gathered and added in rank order, every shard scaled. After
+        accumulate(): the squares of the fp32 sums over micro-batches, and `grad_shard` receives
+        (sum * coef) rounded once to the parameter dtype."""
+        srcs = self._accs if self.micro_batches > 0 else [b.grad_shard.float() for b in self.buckets]
+        sqs = [s.pow(2).sum() for s in srcs]
         recs = gather_sq_records(self.comm, sq_record(sqs))
         self.last_grad_norm, self.last_clip_coef = clip_coef_from_records(recs, self.max_grad_norm)
-        for b in self.buckets:
-            b.grad_shard.mul_(self.last_clip_coef)
+        for b, s in zip(self.buckets, srcs):
+            if self.micro_batches > 0:
+                b.grad_shard.copy_(s * self.last_clip_coef)
+            else:
+                b.grad_shard.mul_(self.last_clip_coef)
 
     # ------------------------------------------------------------------ checkpoint / resume
     def state_dict(self) -> dict:
@@ -300,6 +380,9 @@ class ShardedDataParallel:
         every rank holds them in full, so save `module.state_dict()` once. Tensors are
         references, as in `torch.optim.Optimizer.state_dict`; `torch.save` one file per rank
         and reload with `torch.load(..., weights_only=True)`."""
+        if self.micro_batches > 0:
+            raise RuntimeError(f"state_dict() between accumulate() and step(): {self.micro_batches} micro-batches "
+                               "are held in accumulators, which are scratch and never checkpointed")
         sd = {"world": self.world, "rank": self.rank, "step": self._t, "steps": self.stats["steps"],
               "layout": [[b.numel, str(b.dtype), len(b.params)] for b in self.buckets]}
         if self.fused is not None:
@@ -341,7 +424,11 @@ class ShardedDataParallel:
         self._hooks = []
 
     def describe(self) -> list[dict]:
-        return [{"bucket": b.index, "dtype": str(b.dtype), "params": len(b.params), "numel": b.numel,
+        rows = [{"bucket": b.index, "dtype": str(b.dtype), "params": len(b.params), "numel": b.numel,
                  "shard": b.numel // self.world,
                  "gshard_bytes": 4 * self.gshards[b.index].numel() if getattr(self, "gshards", None) else 0}
                 for b in self.buckets]
+        if self.grad_accumulation:  # the fp32 sums over micro-batches: gshard itself on the fused path
+            for row, b in zip(rows, self.buckets):
+                row["accum_bytes"] = row["gshard_bytes"] if self.fused is not None else 4 * self._accs[b.index].numel()
+        return rows

@@ -446,6 +446,7 @@ void bind_hip(py::module_& m) {
       .def_readonly("coll", &CommStats::coll)
       .def_readonly("adamw", &CommStats::adamw)
       .def_readonly("rs_sq", &CommStats::rs_sq)
+      .def_readonly("rs_sq_acc", &CommStats::rs_sq_acc)
       .def_readonly("adamw_shard", &CommStats::adamw_shard)
       .def_readonly("stream_switches", &CommStats::stream_switches);
 
@@ -694,28 +695,28 @@ void bind_hip(py::module_& m) {
       .def(
           "reduce_scatter_sq",
           [](XgmiComm& c, uintptr_t grads, uintptr_t gshard, uintptr_t sq, int64_t n, DType dt, uintptr_t stream,
-             float scale) {
+             float scale, bool accumulate) {
             py::gil_scoped_release r;
             c.reduce_scatter_sq(as_cptr(grads), reinterpret_cast<float*>(gshard), reinterpret_cast<float*>(sq), n, dt,
-                                as_stream(stream), scale);
+                                as_stream(stream), scale, accumulate);
           },
           py::arg("grads"), py::arg("gshard"), py::arg("sq"), py::arg("n"), py::arg("dtype"), py::arg("stream"),
-          py::arg("scale") = 1.0f)
+          py::arg("scale") = 1.0f, py::arg("accumulate") = false)
       .def_static(
           "reduce_scatter_sq_local",
           [](const std::vector<XgmiComm*>& comms, const std::vector<uintptr_t>& grads,
              const std::vector<uintptr_t>& gshards, const std::vector<uintptr_t>& sqs, int64_t n, DType dt,
-             uintptr_t stream, float scale) {
+             uintptr_t stream, float scale, bool accumulate) {
             std::vector<const void*> g;
             std::vector<float*> gs, sq;
             for (auto x : grads) g.push_back(as_cptr(x));
             for (auto x : gshards) gs.push_back(reinterpret_cast<float*>(x));
             for (auto x : sqs) sq.push_back(reinterpret_cast<float*>(x));
             py::gil_scoped_release r;
-            XgmiComm::reduce_scatter_sq_local(comms, g, gs, sq, n, dt, as_stream(stream), scale);
+            XgmiComm::reduce_scatter_sq_local(comms, g, gs, sq, n, dt, as_stream(stream), scale, accumulate);
           },
           py::arg("comms"), py::arg("grads"), py::arg("gshards"), py::arg("sqs"), py::arg("n"), py::arg("dtype"),
-          py::arg("stream"), py::arg("scale") = 1.0f)
+          py::arg("stream"), py::arg("scale") = 1.0f, py::arg("accumulate") = false)
       .def(
           "step_adamw_shard",
           [](XgmiComm& c, uintptr_t gshard, uintptr_t coef, uintptr_t params, int64_t n, DType dt, uintptr_t stream,

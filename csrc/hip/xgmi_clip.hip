@@ -7,7 +7,10 @@
 //                      fp32 in rank order, times `scale`, stores the fp32 value into its shard
 //                      buffer `gshard` (block_elems elements, block `rank`; nothing past the valid
 //                      length is written) and accumulates its square. The gradients are read
-//                      with nt loads and never written.
+//                      with nt loads and never written. In its accumulating mode (template
+//                      parameter ACC, gradient accumulation over micro-batches) it adds into
+//                      the shard instead: gshard[i] = fl32(gshard[i] + fl32(scale * S[i])), the
+//                      old value read with plain 16-B loads, and squares the new values.
 //   adamw_shard_kernel phases 2 and 3 of the fused step with gshard[i] * coef as the gradient:
 //                      the same adamw() (xgmi_adam_device.h), the master rounded once, the
 //                      write-through pushes to every peer, the gather. `coef` is one fp32 the
@@ -40,7 +43,9 @@
 // rounding to fp32). At 2^28 elements per rank and the default grid (256 workgroups for one
 // rank per device, so L = 2^20): fp32 527 * 2^-24 = 3.1e-5, 16-bit 272 * 2^-24 = 1.6e-5. An
 // explicit grid of 8 workgroups (L = 2^25) gives 16399 * 2^-24 = 9.8e-4 for fp32; below 8
-// workgroups per rank the bound passes 1e-3 for such a block.
+// workgroups per rank the bound passes 1e-3 for such a block. The accumulating mode feeds the
+// NEW shard values through the same tree, unchanged: the bound counts the roundings of the tree
+// from the stored fp32 values on, whatever produced them, so it holds there as it stands.
 //
 // Slot reuse: the reduce-scatter half follows the reduce-scatter of xgmi_coll.hip (entry guard
 // on kHazS, the last workgroup tells the peers when this launch's S reads are done). The
@@ -60,7 +65,16 @@ constexpr int kSqU = 2;  // packs per lane per iteration (the tree above)
 // One reduce unit of the reduce-scatter half: gs[0, len) = scale * sum over ranks (fp32, rank
 // order) and, for every thread, the unit's sum of squares through the tree above. All threads
 // call; lds: 4 floats.
-template <class E, int PT>
+//
+// ACC (gradient accumulation): gs[i] = fl32(gs[i] + fl32(scale * S[i])) and the squares are those
+// of the new values. The product is rounded to fp32 BEFORE the add: left to itself the compiler
+// contracts a * b + c into one fma, whose single rounding differs from the two roundings of
+// plain fp32 ops wherever scale is no power of two (1/3, 1/5), and the accumulated shard would
+// no longer be what `old + plain` gives in torch fp32 on any device. The empty asm pins the
+// product as an fp32 register value (the idiom of adamw(), xgmi_adam_device.h); no instruction.
+// The old values come in with plain 16-B loads (just written by the previous micro-batch, read
+// again by the update half: not nt), issued with the gradient loads before the first use.
+template <class E, int PT, bool ACC>
 __device__ __forceinline__ float reduce_sq_unit(int P, const RedSrc& src, float* gs, int64_t len, float scale,
                                                 float* lds) {
   constexpr int EL = E::ELEMS;
@@ -71,6 +85,7 @@ __device__ __forceinline__ float reduce_sq_unit(int P, const RedSrc& src, float*
   for (int k = 0; k < U * EL; ++k) sq[k] = 0.f;
   for (int64_t i0 = threadIdx.x; i0 < npk; i0 += U * kCommThreads) {
     Acc<E> acc[U];
+    float4 old[U][ACC ? EL / 4 : 1];
     bool live[U];
 #pragma unroll
     for (int w = 0; w < U; ++w) {
@@ -78,6 +93,10 @@ __device__ __forceinline__ float reduce_sq_unit(int P, const RedSrc& src, float*
       live[w] = i < npk;
       acc[w].zero();
       if (!live[w]) continue;
+      if constexpr (ACC) {
+#pragma unroll
+        for (int e = 0; e < EL / 4; ++e) old[w][e] = *reinterpret_cast<const float4*>(gs + i * EL + 4 * e);
+      }
       if constexpr (PT > 0) {
         Pack16 g[PT];
 #pragma unroll
@@ -94,7 +113,11 @@ __device__ __forceinline__ float reduce_sq_unit(int P, const RedSrc& src, float*
       const int64_t i = i0 + w * kCommThreads;
 #pragma unroll
       for (int e = 0; e < EL; ++e) {
-        const float g = acc[w].v[e] * scale;
+        float g = acc[w].v[e] * scale;
+        if constexpr (ACC) {
+          asm("" : "+v"(g));  // fl32(scale * S) first: no fma
+          g += reinterpret_cast<const float*>(&old[w][e / 4])[e % 4];
+        }
         acc[w].v[e] = g;
         sq[w * EL + e] += g * g;
       }
@@ -114,8 +137,14 @@ __device__ __forceinline__ float reduce_sq_unit(int P, const RedSrc& src, float*
   float tail = 0.f;
   if (t < len) {
     float g = 0.f;
+    float old_t = 0.f;
+    if constexpr (ACC) old_t = gs[t];
     for (int s = 0; s < P; ++s) g += ld_scalar_nt<E>(src.rsrc(s), t);
     g *= scale;
+    if constexpr (ACC) {
+      asm("" : "+v"(g));
+      g += old_t;
+    }
     gs[t] = g;
     tail = g * g;
   }
@@ -167,7 +196,7 @@ __device__ __forceinline__ void finish_launch_sq(const CommArgs& a, uint32_t* ct
 
 }  // namespace
 
-template <class E, int PT>
+template <class E, int PT, bool ACC>
 __global__ __launch_bounds__(kCommThreads) void rs_sq_kernel(CommArgs a) {
   constexpr int es = 16 / E::ELEMS;
   __shared__ float wave_sq[4];
@@ -217,7 +246,7 @@ __global__ __launch_bounds__(kCommThreads) void rs_sq_kernel(CommArgs a) {
     float usq = 0.f;  // an empty unit's partial
     if (len > 0 && unit_in_bounds(a, cstart * es, len * es, u, err)) {
       const RedSrc src{grad + (bstart_own + cstart) * es, a.base[r] + a.off_S + cstart * es, slot, r};
-      usq = reduce_sq_unit<E, PT>(P, src, gshard + cstart, len, a.scale, wave_sq);
+      usq = reduce_sq_unit<E, PT, ACC>(P, src, gshard + cstart, len, a.scale, wave_sq);
     }
     if (threadIdx.x == 0) __hip_atomic_store(&part[u], usq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
@@ -424,17 +453,29 @@ __global__ __launch_bounds__(kCommThreads) void adamw_shard_kernel(CommArgs a) {
   finish_launch_done(a, ctl, epoch, r, kHazR);  // peers may still gather from R
 }
 
-void launch_rs_sq(const CommArgs& a, dim3 grid, hipStream_t s, DType dt) {
+namespace {
+
+template <class E, bool ACC>
+void launch_rs_sq_mode(const CommArgs& a, dim3 grid, hipStream_t s) {
+  // static P as in launch_adamw: every source's load issues before the first add
+  switch (a.P) {
+    case 1: hipLaunchKernelGGL((rs_sq_kernel<E, 1, ACC>), grid, dim3(kCommThreads), 0, s, a); break;
+    case 2: hipLaunchKernelGGL((rs_sq_kernel<E, 2, ACC>), grid, dim3(kCommThreads), 0, s, a); break;
+    case 4: hipLaunchKernelGGL((rs_sq_kernel<E, 4, ACC>), grid, dim3(kCommThreads), 0, s, a); break;
+    case 8: hipLaunchKernelGGL((rs_sq_kernel<E, 8, ACC>), grid, dim3(kCommThreads), 0, s, a); break;
+    default: hipLaunchKernelGGL((rs_sq_kernel<E, 0, ACC>), grid, dim3(kCommThreads), 0, s, a); break;
+  }
+}
+
+}  // namespace
+
+void launch_rs_sq(const CommArgs& a, dim3 grid, hipStream_t s, DType dt, bool accumulate) {
   dispatch_dtype(static_cast<int>(dt), [&](auto tag) {
     using E = decltype(tag);
-    // static P as in launch_adamw: every source's load issues before the first add
-    switch (a.P) {
-      case 1: hipLaunchKernelGGL((rs_sq_kernel<E, 1>), grid, dim3(kCommThreads), 0, s, a); break;
-      case 2: hipLaunchKernelGGL((rs_sq_kernel<E, 2>), grid, dim3(kCommThreads), 0, s, a); break;
-      case 4: hipLaunchKernelGGL((rs_sq_kernel<E, 4>), grid, dim3(kCommThreads), 0, s, a); break;
-      case 8: hipLaunchKernelGGL((rs_sq_kernel<E, 8>), grid, dim3(kCommThreads), 0, s, a); break;
-      default: hipLaunchKernelGGL((rs_sq_kernel<E, 0>), grid, dim3(kCommThreads), 0, s, a); break;
-    }
+    if (accumulate)
+      launch_rs_sq_mode<E, true>(a, grid, s);
+    else
+      launch_rs_sq_mode<E, false>(a, grid, s);
   });
 }
 

@@ -567,7 +567,7 @@ CommArgs XgmiComm::clip_args(const std::vector<XgmiComm*>& group, int64_t n, DTy
 
 void XgmiComm::reduce_scatter_sq_local(const std::vector<XgmiComm*>& group, const std::vector<const void*>& grads,
                                        const std::vector<float*>& gshards, const std::vector<float*>& sqs, int64_t n,
-                                       DType dt, hipStream_t stream, float scale) {
+                                       DType dt, hipStream_t stream, float scale, bool accumulate) {
   if (group.empty() || grads.size() != group.size() || gshards.size() != group.size() || sqs.size() != group.size())
     throw std::invalid_argument("reduce_scatter_sq: one grads / gshard / sq per rank");
   const int64_t es = static_cast<int64_t>(dtype_size(dt));
@@ -585,7 +585,8 @@ void XgmiComm::reduce_scatter_sq_local(const std::vector<XgmiComm*>& group, cons
   dim3 grid;
   CommArgs a = clip_args(group, n, dt, "reduce_scatter_sq", stream, &grid);
   TraceScope span("xgmi", [&] {
-    return std::make_pair("rs_sq " + std::to_string(n * es) + "B", "{\"rank\":" + std::to_string(group[0]->rank_) + "}");
+    return std::make_pair(std::string(accumulate ? "rs_sq_acc " : "rs_sq ") + std::to_string(n * es) + "B",
+                          "{\"rank\":" + std::to_string(group[0]->rank_) + "}");
   });
   for (size_t y = 0; y < group.size(); ++y) {
     XgmiComm& c = *group[y];
@@ -597,17 +598,18 @@ void XgmiComm::reduce_scatter_sq_local(const std::vector<XgmiComm*>& group, cons
     a.sq_out[y] = sqs[y];
   }
   a.scale = scale;
-  launch_rs_sq(a, grid, stream, dt);
+  launch_rs_sq(a, grid, stream, dt, accumulate);
   hip_check(hipGetLastError(), "rs_sq launch");
   for (XgmiComm* c : group) {
     ++c->stats_.launches;
     ++c->stats_.rs_sq;
+    if (accumulate) ++c->stats_.rs_sq_acc;
   }
 }
 
 void XgmiComm::reduce_scatter_sq(const void* grads, float* gshard, float* sq, int64_t n, DType dt, hipStream_t stream,
-                                 float scale) {
-  reduce_scatter_sq_local({this}, {grads}, {gshard}, {sq}, n, dt, stream, scale);
+                                 float scale, bool accumulate) {
+  reduce_scatter_sq_local({this}, {grads}, {gshard}, {sq}, n, dt, stream, scale, accumulate);
 }
 
 void XgmiComm::step_adamw_shard_local(const std::vector<XgmiComm*>& group, const std::vector<const float*>& gshards,

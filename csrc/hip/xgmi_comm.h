@@ -54,6 +54,8 @@ struct CommStats {
            adamw = 0, stream_switches = 0;
   // the clipped step's halves (xgmi_clip.hip): they count here, not in `adamw` or `coll`
   uint64_t rs_sq = 0, adamw_shard = 0;
+  // reduce_scatter_sq launches in accumulating mode (they count in rs_sq too)
+  uint64_t rs_sq_acc = 0;
 };
 
 class XgmiComm {
@@ -254,12 +256,14 @@ class XgmiComm {
   // reduce_scatter_sq: grads [n] of every rank are reduce-scattered (x scale, fp32, rank order)
   // into gshard (fp32, block_elems(n) elements, block `rank`; nothing past the valid length is
   // written) and *sq = the sum of the squares of this rank's shard (device fp32; fixed summation
-  // tree, see the kernel file). The gradients are not written.
+  // tree, see the kernel file). The gradients are not written. accumulate (gradient accumulation
+  // over micro-batches): gshard[i] = fl32(gshard[i] + fl32(scale * sum)) instead, *sq over the
+  // new values; gshard must then hold defined values in its valid part.
   void reduce_scatter_sq(const void* grads, float* gshard, float* sq, int64_t n, DType dt, hipStream_t stream,
-                         float scale);
+                         float scale, bool accumulate = false);
   static void reduce_scatter_sq_local(const std::vector<XgmiComm*>& comms, const std::vector<const void*>& grads,
                                       const std::vector<float*>& gshards, const std::vector<float*>& sqs, int64_t n,
-                                      DType dt, hipStream_t stream, float scale);
+                                      DType dt, hipStream_t stream, float scale, bool accumulate = false);
   // step_adamw_shard: AdamW on the shard state with gshard[i] * *coef as the gradient (coef: a
   // device fp32), the updated parameters all-gathered into `params` [n] as step_adamw does.
   void step_adamw_shard(const float* gshard, const float* coef, void* params, int64_t n, DType dt,

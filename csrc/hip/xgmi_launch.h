@@ -28,7 +28,8 @@ void launch_ll(const CommArgs& a, dim3 grid, hipStream_t s, DType dt);
 void launch_adamw(const CommArgs& a, dim3 grid, hipStream_t s, DType dt);
 // Host entries of the clipped step's two halves (xgmi_clip.hip): reduce-scatter into the fp32
 // shard with the sum of squares; AdamW from the shard times the clip coefficient + all-gather.
-void launch_rs_sq(const CommArgs& a, dim3 grid, hipStream_t s, DType dt);
+// accumulate: gshard += the scaled sum (fp32, product rounded before the add) instead of =
+void launch_rs_sq(const CommArgs& a, dim3 grid, hipStream_t s, DType dt, bool accumulate);
 void launch_adamw_shard(const CommArgs& a, dim3 grid, hipStream_t s, DType dt);
 // Host entry of all-to-all (mode 0) / all-gather (1) / reduce-scatter (2) (xgmi_coll.hip).
 void launch_coll(const CommArgs& a, dim3 grid, hipStream_t s, DType dt, int mode);
