@@ -12,8 +12,8 @@
 //                      the shard instead: gshard[i] = fl32(gshard[i] + fl32(scale * S[i])), the
 //                      old value read with plain 16-B loads, and squares the new values.
 //   adamw_shard_kernel phases 2 and 3 of the fused step with gshard[i] * coef as the gradient:
-//                      the same adamw() (xgmi_adam_device.h), the master rounded once, the
-//                      write-through pushes to every peer, the gather. `coef` is one fp32 the
+//                      the same adamw_unit (xgmi_adam_device.h: adamw(), the master rounded once,
+//                      the write-through pushes to every peer) and gather. `coef` is one fp32 the
 //                      host side computed on the device from every rank's sum of squares.
 //
 // Between the two, 8 B per owned parameter go through HBM that the fused step keeps in
@@ -200,257 +200,62 @@ template <class E, int PT, bool ACC>
 __global__ __launch_bounds__(kCommThreads) void rs_sq_kernel(CommArgs a) {
   constexpr int es = 16 / E::ELEMS;
   __shared__ float wave_sq[4];
-  const int P = PT > 0 ? PT : a.P;
+  const StepCtx k(a, PT > 0 ? PT : a.P);
   const int y = blockIdx.y;
-  const int r = a.rank0 + y;
+  const int r = k.r;
   const char* const grad = a.in[y];
+  const int64_t slot = a.slot_bytes;  // read once, here: see twoshot_adamw_kernel (xgmi_adam.hip)
   float* const gshard = a.gshard[y];
   float* const part = a.sq_part[y];
-  uint32_t* const ctl = a.ctl[y];
-  const uint32_t epoch = launch_epoch(ctl);
-  const uint64_t deadline = wall_ticks() + a.timeout;
-  const int G = gridDim.x;
-  const int64_t slot = a.slot_bytes;
-  uint32_t* err = &ctl[2];
-  const bool rel = a.fence & 1, acq = a.fence & 2;
-  const int Pm1 = P > 1 ? P - 1 : 1;
-  const int nu = (P - 1) * a.nch;
 
   // Phase 1 - gradient ScatterBlock: chunk c of block j to its owner j
-  if (static_cast<int>(blockIdx.x) < nu) entry_guard(a, ctl, r, epoch, kHazS, -1, deadline, err);
-  for (int u = blockIdx.x; u < nu; u += G) {
-    const int c = u / Pm1;
-    const int j = (r + 1 + u % Pm1) % P;
-    const int64_t bstart = static_cast<int64_t>(j) * a.block;
-    const int64_t cstart = static_cast<int64_t>(c) * a.chunk;
-    const int64_t len = clamp_len(clamp_len(a.n - bstart, a.block) - cstart, a.chunk);
-    if (len > 0 && unit_in_bounds(a, cstart * es, len * es, c, err))
-      copy_to_slab<E>(a.base[j] + a.off_S + r * slot + cstart * es, grad + (bstart + cstart) * es, len);
-    publish_flags([&](int) { return f1(a, j, r, c); }, 1, epoch, rel);
-  }
+  if (static_cast<int>(blockIdx.x) < k.nu) entry_guard(a, k.ctl, r, k.epoch, kHazS, -1, k.deadline, k.err);
+  scatter_grads<E>(a, k, grad);
 
   read_delay(a, r);
   // Phase 2 - reduce own chunk into the fp32 shard, one partial sum of squares per unit
   const int64_t bstart_own = static_cast<int64_t>(r) * a.block;
-  const int64_t blen_own = clamp_len(a.n - bstart_own, a.block);
   const int nu2 = a.nch * a.sub;
-  for (int u = blockIdx.x; u < nu2; u += G) {
-    const int c = u / a.sub;
-    const int q = u % a.sub;
-    const int64_t cbeg = static_cast<int64_t>(c) * a.chunk;
-    const int64_t qbeg = static_cast<int64_t>(q) * a.subchunk;
-    const int64_t cstart = cbeg + qbeg;
-    const int64_t len = clamp_len(clamp_len(blen_own - cbeg, a.chunk) - qbeg, a.subchunk);
-    wait_flags([&](int s) -> const uint32_t* { return s == r ? nullptr : f1(a, r, s, c); }, P, epoch, deadline, err,
-               ERR_TIMEOUT_SCATTER, acq);
+  for (int u = blockIdx.x; u < nu2; u += k.G) {
+    const OwnUnit o = own_unit(a, r, u);
+    wait_flags([&](int s) -> const uint32_t* { return s == r ? nullptr : f1(a, r, s, o.c); }, k.P, k.epoch, k.deadline,
+               k.err, ERR_TIMEOUT_SCATTER, k.acq);
     float usq = 0.f;  // an empty unit's partial
-    if (len > 0 && unit_in_bounds(a, cstart * es, len * es, u, err)) {
-      const RedSrc src{grad + (bstart_own + cstart) * es, a.base[r] + a.off_S + cstart * es, slot, r};
-      usq = reduce_sq_unit<E, PT, ACC>(P, src, gshard + cstart, len, a.scale, wave_sq);
+    if (o.len > 0 && unit_in_bounds(a, o.cstart * es, o.len * es, u, k.err)) {
+      const RedSrc src{grad + (bstart_own + o.cstart) * es, a.base[r] + a.off_S + o.cstart * es, slot, r};
+      usq = reduce_sq_unit<E, PT, ACC>(k.P, src, gshard + o.cstart, o.len, a.scale, wave_sq);
     }
     if (threadIdx.x == 0) __hip_atomic_store(&part[u], usq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
-  finish_launch_sq(a, ctl, epoch, r, part, nu2, a.sq_out[y]);  // peers may still reduce what was pushed into S
+  finish_launch_sq(a, k.ctl, k.epoch, r, part, nu2, a.sq_out[y]);  // peers may still reduce what was pushed into S
 }
 
-// The update half. The body of a reduce unit is the text of twoshot_adamw_kernel's (xgmi_adam.hip)
-// written in the kernel as it is there, with ONE gradient source - the fp32 shard, summed into the
-// zeroed accumulator through the loops of the fused step's P-way sum - and the coefficient where
-// the fused step has its scale: the compiler orders and contracts the products of adamw() by
-// the code around them, and only the same text in the same place gave the fused step's bits
-// (tests/test_clip_gpu.py holds the two kernels bit for bit against each other).
+// The update half: phases 2 and 3 of the fused step through the same adamw_unit and
+// gather_params (xgmi_adam_device.h), with the fp32 shard times the clip coefficient as the
+// gradient. tests/test_clip_gpu.py holds the two gradient sources bit for bit against each other.
 template <class E, int STREAM, int U>
 __global__ __launch_bounds__(kCommThreads) void adamw_shard_kernel(CommArgs a) {
   constexpr int es = 16 / E::ELEMS;
-  constexpr int EL = E::ELEMS;
-  constexpr int PT = 1;  // gradient sources
-  const int P = a.P;
+  const StepCtx k(a, a.P);
   const int y = blockIdx.y;
-  const int r = a.rank0 + y;
+  const int r = k.r;
   const float* const gshard = a.gshard[y];
   const float coef = *a.coef[y];
-  char* const param = a.out[y];
-  float* const mp = a.opt_p[y];
-  float* const m1 = a.opt_m[y];
-  float* const m2 = a.opt_v[y];
-  uint32_t* const ctl = a.ctl[y];
-  const uint32_t epoch = launch_epoch(ctl);
-  const uint64_t deadline = wall_ticks() + a.timeout;
-  const int G = gridDim.x;
-  const int64_t slot = a.slot_bytes;
-  uint32_t* err = &ctl[2];
-  const bool rel = a.fence & 1, acq = a.fence & 2;
-  const int Pm1 = P > 1 ? P - 1 : 1;
-  const int nu = (P - 1) * a.nch;
 
   // AdamW on the owned shard, push the new parameters (phase 2 of the fused step). The pushes
   // go into R slots the peers may still be reading in the previous launch: entry guard.
-  const int64_t bstart_own = static_cast<int64_t>(r) * a.block;
-  const int64_t blen_own = clamp_len(a.n - bstart_own, a.block);
   const int nu2 = a.nch * a.sub;
-  if (P > 1 && static_cast<int>(blockIdx.x) < nu2) entry_guard(a, ctl, r, epoch, kHazR, -1, deadline, err);
-  for (int u = blockIdx.x; u < nu2; u += G) {
-    const int c = u / a.sub;
-    const int q = u % a.sub;
-    const int64_t cbeg = static_cast<int64_t>(c) * a.chunk;
-    const int64_t qbeg = static_cast<int64_t>(q) * a.subchunk;
-    const int64_t cstart = cbeg + qbeg;
-    const int64_t len = clamp_len(clamp_len(blen_own - cbeg, a.chunk) - qbeg, a.subchunk);
-    if (len > 0 && unit_in_bounds(a, cstart * es, len * es, u, err)) {
-      const __amdgpu_buffer_rsrc_t rg = slab_rsrc(gshard + cstart);  // read once: nt loads
-      char* own_out = param + (bstart_own + cstart) * es;
-      const int64_t roff = a.off_R + r * slot + cstart * es;
-      float* const sp = mp + cstart;
-      float* const sm = m1 + cstart;
-      float* const sv = m2 + cstart;
-      const __amdgpu_buffer_rsrc_t rp = slab_rsrc(sp), rm = slab_rsrc(sm), rv = slab_rsrc(sv);
-      const int64_t npk = len / EL;
-      if constexpr (STREAM == 3 && EL == 8) {
-        // Run-contiguous halves (16-bit parameters, the default): lane l of a run of 256 packs
-        // takes elements [4l, 4l + 4) of each half of the run's 2048 elements, so every fp32
-        // state load / store instruction of a wave covers 1 KiB of consecutive bytes and every
-        // 16-bit one 512 B. (One 16-B parameter pack per lane made each fp32 state access hit
-        // every other 16 B of 2 KiB: half-written lines, 15.3 B written per parameter instead
-        // of 14 - profiles/round4/README.md section 5.) The last, short run is split the same
-        // way with `rows` lanes per half. Scatter and gather stay plain contiguous copies.
-        auto eoff = [&](int64_t i, int h) -> int64_t {
-          const int64_t run = i / kCommThreads;
-          const int64_t l = i - run * kCommThreads;
-          const int64_t left = npk - run * kCommThreads;
-          const int64_t rows = left < kCommThreads ? left : kCommThreads;
-          return run * kCommThreads * EL + h * rows * 4 + l * 4;
-        };
-        for (int64_t i0 = threadIdx.x; i0 < npk; i0 += U * kCommThreads) {
-          Acc8<E> acc[U][2];
-          float4 p4[U][2], m4[U][2], v4[U][2];
-          bool live[U];
-#pragma unroll
-          for (int w = 0; w < U; ++w) {
-            const int64_t i = i0 + w * kCommThreads;
-            live[w] = i < npk;
-            if (!live[w]) continue;
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-              const int64_t e0 = eoff(i, h);
-              Pack16 g[PT];
-#pragma unroll
-              for (int s = 0; s < PT; ++s) g[s] = ld16_nt(rg, static_cast<uint32_t>(e0 * 4));
-#pragma unroll
-              for (int s = 0; s < PT; ++s) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) acc[w][h].v[k] += __uint_as_float(g[s][k]);
-              }
-              p4[w][h] = *reinterpret_cast<const float4*>(sp + e0);
-              m4[w][h] = *reinterpret_cast<const float4*>(sm + e0);
-              v4[w][h] = *reinterpret_cast<const float4*>(sv + e0);
-            }
-          }
-#pragma unroll
-          for (int w = 0; w < U; ++w) {
-            if (!live[w]) continue;
-            const int64_t i = i0 + w * kCommThreads;
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-              const int64_t e0 = eoff(i, h);
-              Acc8<E>& ac = acc[w][h];
-              ac.v[0] = adamw(ac.v[0] * coef, &p4[w][h].x, &m4[w][h].x, &v4[w][h].x, a);
-              ac.v[1] = adamw(ac.v[1] * coef, &p4[w][h].y, &m4[w][h].y, &v4[w][h].y, a);
-              ac.v[2] = adamw(ac.v[2] * coef, &p4[w][h].z, &m4[w][h].z, &v4[w][h].z, a);
-              ac.v[3] = adamw(ac.v[3] * coef, &p4[w][h].w, &m4[w][h].w, &v4[w][h].w, a);
-              *reinterpret_cast<float4*>(sp + e0) = p4[w][h];
-              *reinterpret_cast<float4*>(sm + e0) = m4[w][h];
-              *reinterpret_cast<float4*>(sv + e0) = v4[w][h];
-              const uint2 o = ac.pack(1.f);
-              *reinterpret_cast<uint2*>(own_out + e0 * 2) = o;
-              typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-              const u32x2 ov = {o.x, o.y};
-              for (int k = 0; k < P; ++k)
-                if (k != r)
-                  __builtin_amdgcn_raw_buffer_store_b64(ov, slab_rsrc(a.base[k] + roff), static_cast<int>(e0 * 2), 0,
-                                                        kAuxWt);
-            }
-          }
-        }
-      } else
-      // U packs per lane per iteration, every load issued before the first use: the
-      // persistent grid has only 2 workgroups per CU, so bytes in flight come from ILP
-      for (int64_t i0 = threadIdx.x; i0 < npk; i0 += U * kCommThreads) {
-        Acc<E> acc[U];
-        float4 p4[U][EL / 4], m4[U][EL / 4], v4[U][EL / 4];
-        bool live[U];
-#pragma unroll
-        for (int w = 0; w < U; ++w) {
-          const int64_t i = i0 + w * kCommThreads;
-          live[w] = i < npk;
-          acc[w].zero();
-          if (!live[w]) continue;
-#pragma unroll
-          for (int e = 0; e < EL / 4; ++e) {
-            Pack16 g[PT];
-#pragma unroll
-            for (int s = 0; s < PT; ++s) g[s] = ld16_nt(rg, static_cast<uint32_t>((i * EL + 4 * e) * 4));
-#pragma unroll
-            for (int s = 0; s < PT; ++s) {
-#pragma unroll
-              for (int k = 0; k < 4; ++k) acc[w].v[4 * e + k] += __uint_as_float(g[s][k]);
-            }
-          }
-#pragma unroll
-          for (int e = 0; e < EL / 4; ++e) {
-            p4[w][e] = ld_state<STREAM>(sp, rp, i * EL + 4 * e);
-            m4[w][e] = ld_state<STREAM>(sm, rm, i * EL + 4 * e);
-            v4[w][e] = ld_state<STREAM>(sv, rv, i * EL + 4 * e);
-          }
-        }
-#pragma unroll
-        for (int w = 0; w < U; ++w) {
-          if (!live[w]) continue;
-          const int64_t i = i0 + w * kCommThreads;
-#pragma unroll
-          for (int e = 0; e < EL / 4; ++e) {
-            acc[w].v[4 * e + 0] = adamw(acc[w].v[4 * e + 0] * coef, &p4[w][e].x, &m4[w][e].x, &v4[w][e].x, a);
-            acc[w].v[4 * e + 1] = adamw(acc[w].v[4 * e + 1] * coef, &p4[w][e].y, &m4[w][e].y, &v4[w][e].y, a);
-            acc[w].v[4 * e + 2] = adamw(acc[w].v[4 * e + 2] * coef, &p4[w][e].z, &m4[w][e].z, &v4[w][e].z, a);
-            acc[w].v[4 * e + 3] = adamw(acc[w].v[4 * e + 3] * coef, &p4[w][e].w, &m4[w][e].w, &v4[w][e].w, a);
-            st_state<STREAM>(sp, rp, i * EL + 4 * e, p4[w][e]);
-            st_state<STREAM>(sm, rm, i * EL + 4 * e, m4[w][e]);
-            st_state<STREAM>(sv, rv, i * EL + 4 * e, v4[w][e]);
-          }
-          const Pack16 o = acc[w].pack();
-          if constexpr (STREAM == 1)
-            st16_wt(slab_rsrc(own_out), static_cast<uint32_t>(i * 16), o);
-          else
-            st16(own_out + i * 16, o);
-          for (int k = 0; k < P; ++k)
-            if (k != r) st16_wt(slab_rsrc(a.base[k] + roff), static_cast<uint32_t>(i * 16), o);
-        }
-      }
-      const int64_t t = npk * EL + threadIdx.x;
-      if (t < len) {
-        float g = 0.f;
-        for (int s = 0; s < PT; ++s) g += ld_scalar_nt<F32>(rg, t);
-        const float pv = adamw(g * coef, sp + t, sm + t, sv + t, a);
-        Scalar<E>::store(own_out, t, pv);
-        for (int k = 0; k < P; ++k)
-          if (k != r) st_scalar_wt<E>(slab_rsrc(a.base[k] + roff), t, pv);
-      }
-    }
-    publish_flags([&](int k) -> uint32_t* { return k == r ? nullptr : f2(a, k, r, u); }, P, epoch, rel);
+  if (k.P > 1 && static_cast<int>(blockIdx.x) < nu2) entry_guard(a, k.ctl, r, k.epoch, kHazR, -1, k.deadline, k.err);
+  for (int u = blockIdx.x; u < nu2; u += k.G) {
+    const OwnUnit o = own_unit(a, r, u);
+    if (o.len > 0 && unit_in_bounds(a, o.cstart * es, o.len * es, u, k.err))
+      adamw_unit<E, STREAM, U>(a, k.P, r, o.cstart, o.len, ShardGrad<E>{slab_rsrc(gshard + o.cstart), coef});
+    publish_flags([&](int p) -> uint32_t* { return p == r ? nullptr : f2(a, p, r, u); }, k.P, k.epoch, k.rel);
   }
 
   // Gather the other owners' updated parameter chunks (phase 3 of the fused step)
-  for (int u = blockIdx.x; u < nu; u += G) {
-    const int c = u / Pm1;
-    const int j = (r + 1 + u % Pm1) % P;
-    const int64_t bstart = static_cast<int64_t>(j) * a.block;
-    const int64_t cstart = static_cast<int64_t>(c) * a.chunk;
-    const int64_t len = clamp_len(clamp_len(a.n - bstart, a.block) - cstart, a.chunk);
-    wait_flags([&](int q) -> const uint32_t* { return f2(a, r, j, c * a.sub + q); }, a.sub, epoch, deadline, err,
-               ERR_TIMEOUT_REDUCE, acq);
-    if (len > 0 && unit_in_bounds(a, cstart * es, len * es, c, err))
-      copy_from_slab<E>(param + (bstart + cstart) * es, a.base[r] + a.off_R + j * slot + cstart * es, len);
-  }
-  finish_launch_done(a, ctl, epoch, r, kHazR);  // peers may still gather from R
+  gather_params<E>(a, k, a.out[y]);
+  finish_launch_done(a, k.ctl, k.epoch, r, kHazR);  // peers may still gather from R
 }
 
 namespace {

@@ -366,14 +366,13 @@ static void set_adamw_hyper(CommArgs& a, const AdamW& h) {
 // One launch for the ranks `group` (all on one device, consecutive rank ids starting at
 // group[0]->rank()) over one segment of n elements.
 void XgmiComm::launch_segment(const std::vector<XgmiComm*>& group, const char* const* ins, char* const* outs,
-                              int64_t n, DType dt, hipStream_t stream, Algo kind, float scale,
-                              const std::vector<AdamShard>* adam_state, const AdamW* adam) {
+                              int64_t n, DType dt, hipStream_t stream, Algo kind, float scale) {
   const bool oneshot = kind == Algo::OneShot;
   const bool ring = kind == Algo::Ring || kind == Algo::RingNative;
   const XgmiComm& c0 = *group[0];
   const int64_t es = static_cast<int64_t>(dtype_size(dt));
   const int ranks_here = static_cast<int>(group.size());
-  const LaunchGeometry g = plan_allreduce(kind, c0.knobs(), n, es, ranks_here, adam_state != nullptr);
+  const LaunchGeometry g = plan_allreduce(kind, c0.knobs(), n, es, ranks_here);
   CommArgs a = c0.base_args(group);
   for (size_t y = 0; y < group.size(); ++y) {
     a.in[y] = ins[y];
@@ -390,21 +389,6 @@ void XgmiComm::launch_segment(const std::vector<XgmiComm*>& group, const char* c
   a.stamps = c0.stamps_;
   if (a.stamps != nullptr && g.gx * ranks_here > c0.stamp_slots_) a.stamps = nullptr;  // buffer too small: off
   const dim3 grid(g.gx, ranks_here);
-  if (adam != nullptr) {
-    for (size_t y = 0; y < group.size(); ++y) {
-      a.opt_p[y] = (*adam_state)[y].param;
-      a.opt_m[y] = (*adam_state)[y].exp_avg;
-      a.opt_v[y] = (*adam_state)[y].exp_avg_sq;
-    }
-    set_adamw_hyper(a, *adam);
-    launch_adamw(a, grid, stream, dt);
-    hip_check(hipGetLastError(), "adamw launch");
-    for (XgmiComm* c : group) {
-      ++c->stats_.launches;
-      ++c->stats_.adamw;
-    }
-    return;
-  }
   if (kind == Algo::LL) {
     if (2 * ceil_div(n * es, 8) * 8 > c0.ll_slot_) throw std::logic_error("XgmiComm: LL segment exceeds its slot");
     launch_ll(a, grid, stream, dt);
@@ -484,62 +468,17 @@ int64_t XgmiComm::block_elems(int64_t n, DType dt) const {
   return mxar::block_elems(world_, n, static_cast<int64_t>(dtype_size(dt)));
 }
 
-void XgmiComm::step_adamw_local(const std::vector<XgmiComm*>& group, const std::vector<const void*>& grads,
-                                const std::vector<void*>& params, int64_t n, DType dt, hipStream_t stream,
-                                const std::vector<AdamShard>& st, const AdamW& h, float scale) {
-  if (group.empty() || grads.size() != group.size() || params.size() != group.size() || st.size() != group.size())
-    throw std::invalid_argument("step_adamw: one grads / params / shard state per rank");
-  const XgmiComm& c0 = *group[0];
-  const int64_t es = static_cast<int64_t>(dtype_size(dt));
-  for (size_t y = 0; y < group.size(); ++y) {
-    const XgmiComm& c = *group[y];
-    if (!c.connected_) throw std::runtime_error("XgmiComm: connect() first");
-    if (c.device_ != c0.device_ || c.rank_ != c0.rank_ + static_cast<int>(y) || c.world_ != c0.world_)
-      throw std::invalid_argument("XgmiComm: a grouped launch needs consecutive ranks on one device");
-    const uintptr_t g = reinterpret_cast<uintptr_t>(grads[y]), p = reinterpret_cast<uintptr_t>(params[y]);
-    if ((g | p | reinterpret_cast<uintptr_t>(st[y].param) | reinterpret_cast<uintptr_t>(st[y].exp_avg) |
-         reinterpret_cast<uintptr_t>(st[y].exp_avg_sq)) & 15)
-      throw std::invalid_argument("step_adamw: buffers must be 16-byte aligned");
-    if (g < p + static_cast<uintptr_t>(n * es) && p < g + static_cast<uintptr_t>(n * es))
-      throw std::invalid_argument("step_adamw: grads and params must not overlap");
-  }
-  if (n <= 0) return;
-  if (n * es > c0.world_ * c0.slot_bytes_)
-    throw std::invalid_argument("step_adamw: tensor exceeds one launch (n * dtype <= world * slot_bytes)");
-  if (h.step < 1) throw std::invalid_argument("step_adamw: step counts from 1");
-  hip_check(hipSetDevice(c0.device_), "hipSetDevice");
-  for (XgmiComm* c : group) {
-    ++c->stats_.calls;
-    c->stats_.bytes += n * es;
-  }
-  order_group(group, stream);
-  TraceScope span("xgmi", [&] {
-    return std::make_pair("adamw " + std::to_string(n * es) + "B", "{\"rank\":" + std::to_string(c0.rank_) + "}");
-  });
-  std::vector<const char*> ip(group.size());
-  std::vector<char*> op(group.size());
-  for (size_t y = 0; y < group.size(); ++y) {
-    ip[y] = static_cast<const char*>(grads[y]);
-    op[y] = static_cast<char*>(params[y]);
-  }
-  launch_segment(group, ip.data(), op.data(), n, dt, stream, Algo::TwoShot, scale, &st, &h);
-}
-
-void XgmiComm::step_adamw(const void* grads, void* params, int64_t n, DType dt, hipStream_t stream,
-                          const AdamShard& st, const AdamW& h, float scale) {
-  step_adamw_local({this}, {grads}, {params}, n, dt, stream, {st}, h, scale);
-}
-
 // ---------------------------------------------------------------------------------
-// The clipped step (xgmi_clip.hip): the fused step in two launches on its geometry
+// The sharded-data-parallel step: fused (xgmi_adam.hip), or in two launches where a global
+// gradient norm is wanted (xgmi_clip.hip) - all three entry points on the `adamw` geometry
 // ---------------------------------------------------------------------------------
 static bool overlaps(const void* a, int64_t abytes, const void* b, int64_t bbytes) {
   const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
   return x < y + static_cast<uintptr_t>(bbytes) && y < x + static_cast<uintptr_t>(abytes);
 }
 
-CommArgs XgmiComm::clip_args(const std::vector<XgmiComm*>& group, int64_t n, DType dt, const char* what,
-                             hipStream_t stream, dim3* grid) {
+CommArgs XgmiComm::shard_step_args(const std::vector<XgmiComm*>& group, int64_t n, DType dt, const char* what,
+                                   hipStream_t stream, dim3* grid) {
   const XgmiComm& c0 = *group[0];
   const int64_t es = static_cast<int64_t>(dtype_size(dt));
   for (size_t y = 0; y < group.size(); ++y) {
@@ -565,6 +504,49 @@ CommArgs XgmiComm::clip_args(const std::vector<XgmiComm*>& group, int64_t n, DTy
   return a;
 }
 
+void XgmiComm::step_adamw_local(const std::vector<XgmiComm*>& group, const std::vector<const void*>& grads,
+                                const std::vector<void*>& params, int64_t n, DType dt, hipStream_t stream,
+                                const std::vector<AdamShard>& st, const AdamW& h, float scale) {
+  if (group.empty() || grads.size() != group.size() || params.size() != group.size() || st.size() != group.size())
+    throw std::invalid_argument("step_adamw: one grads / params / shard state per rank");
+  const int64_t es = static_cast<int64_t>(dtype_size(dt));
+  for (size_t y = 0; y < group.size(); ++y) {
+    if ((reinterpret_cast<uintptr_t>(grads[y]) | reinterpret_cast<uintptr_t>(params[y]) |
+         reinterpret_cast<uintptr_t>(st[y].param) | reinterpret_cast<uintptr_t>(st[y].exp_avg) |
+         reinterpret_cast<uintptr_t>(st[y].exp_avg_sq)) & 15)
+      throw std::invalid_argument("step_adamw: buffers must be 16-byte aligned");
+    if (overlaps(grads[y], n * es, params[y], n * es))
+      throw std::invalid_argument("step_adamw: grads and params must not overlap");
+  }
+  if (n <= 0) return;
+  if (h.step < 1) throw std::invalid_argument("step_adamw: step counts from 1");
+  dim3 grid;
+  CommArgs a = shard_step_args(group, n, dt, "step_adamw", stream, &grid);
+  TraceScope span("xgmi", [&] {
+    return std::make_pair("adamw " + std::to_string(n * es) + "B", "{\"rank\":" + std::to_string(group[0]->rank_) + "}");
+  });
+  for (size_t y = 0; y < group.size(); ++y) {
+    a.in[y] = static_cast<const char*>(grads[y]);
+    a.out[y] = static_cast<char*>(params[y]);
+    a.opt_p[y] = st[y].param;
+    a.opt_m[y] = st[y].exp_avg;
+    a.opt_v[y] = st[y].exp_avg_sq;
+  }
+  a.scale = scale;
+  set_adamw_hyper(a, h);
+  launch_adamw(a, grid, stream, dt);
+  hip_check(hipGetLastError(), "adamw launch");
+  for (XgmiComm* c : group) {
+    ++c->stats_.launches;
+    ++c->stats_.adamw;
+  }
+}
+
+void XgmiComm::step_adamw(const void* grads, void* params, int64_t n, DType dt, hipStream_t stream,
+                          const AdamShard& st, const AdamW& h, float scale) {
+  step_adamw_local({this}, {grads}, {params}, n, dt, stream, {st}, h, scale);
+}
+
 void XgmiComm::reduce_scatter_sq_local(const std::vector<XgmiComm*>& group, const std::vector<const void*>& grads,
                                        const std::vector<float*>& gshards, const std::vector<float*>& sqs, int64_t n,
                                        DType dt, hipStream_t stream, float scale, bool accumulate) {
@@ -583,7 +565,7 @@ void XgmiComm::reduce_scatter_sq_local(const std::vector<XgmiComm*>& group, cons
   }
   if (n <= 0) return;
   dim3 grid;
-  CommArgs a = clip_args(group, n, dt, "reduce_scatter_sq", stream, &grid);
+  CommArgs a = shard_step_args(group, n, dt, "reduce_scatter_sq", stream, &grid);
   TraceScope span("xgmi", [&] {
     return std::make_pair(std::string(accumulate ? "rs_sq_acc " : "rs_sq ") + std::to_string(n * es) + "B",
                           "{\"rank\":" + std::to_string(group[0]->rank_) + "}");
@@ -637,7 +619,7 @@ void XgmiComm::step_adamw_shard_local(const std::vector<XgmiComm*>& group, const
   if (n <= 0) return;
   if (h.step < 1) throw std::invalid_argument("step_adamw_shard: step counts from 1");
   dim3 grid;
-  CommArgs a = clip_args(group, n, dt, "step_adamw_shard", stream, &grid);
+  CommArgs a = shard_step_args(group, n, dt, "step_adamw_shard", stream, &grid);
   TraceScope span("xgmi", [&] {
     return std::make_pair("adamw_shard " + std::to_string(n * es) + "B",
                           "{\"rank\":" + std::to_string(group[0]->rank_) + "}");

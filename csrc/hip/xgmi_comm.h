@@ -373,17 +373,17 @@ class XgmiComm {
   static void run(const std::vector<XgmiComm*>& group, const std::vector<const void*>& ins,
                   const std::vector<void*>& outs, int64_t n, DType dt, hipStream_t stream, Algo algo, float scale);
   static void launch_segment(const std::vector<XgmiComm*>& group, const char* const* ins, char* const* outs,
-                             int64_t n, DType dt, hipStream_t stream, Algo kind, float scale,
-                             const std::vector<AdamShard>* adam_state = nullptr, const AdamW* adam = nullptr);
+                             int64_t n, DType dt, hipStream_t stream, Algo kind, float scale);
 
   static void run_coll(const std::vector<XgmiComm*>& group, Coll op, const std::vector<const void*>& ins,
                        const std::vector<void*>& outs, int64_t m, DType dt, hipStream_t stream, float scale);
   static void run_rooted(const std::vector<XgmiComm*>& group, Rooted kind, const std::vector<const void*>& ins,
                          const std::vector<void*>& outs, int64_t n, DType dt, int root, hipStream_t stream,
                          float scale);
-  // The clipped step's halves: group checks, stats, stream order and the `adamw` geometry
-  static CommArgs clip_args(const std::vector<XgmiComm*>& group, int64_t n, DType dt, const char* what,
-                            hipStream_t stream, dim3* grid);
+  // The fused step and the clipped step's halves: group checks, the one-launch size limit,
+  // stats, stream order and the `adamw` geometry
+  static CommArgs shard_step_args(const std::vector<XgmiComm*>& group, int64_t n, DType dt, const char* what,
+                                  hipStream_t stream, dim3* grid);
   // The fields every launch of `group` shares: membership, slab layout, timeout, fence, peers.
   CommArgs base_args(const std::vector<XgmiComm*>& group) const;
   // A grouped launch: connected, consecutive ranks on one device (need_rows: and one lag ring

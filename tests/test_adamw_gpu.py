@@ -238,7 +238,7 @@ def _f32(x):
 
 def _host_constants(b1, b2, t):
     """c1 = 1 - beta1^t and c2_sqrt = sqrt(1 - beta2^t) formed in float32 from the float32
-    betas, as launch_segment forms them; the powers are the correctly rounded ones (float64 pow,
+    betas, as set_adamw_hyper forms them; the powers are the correctly rounded ones (float64 pow,
     rounded once). Returns (c1, c2_sqrt, beta1^t, beta2^t) as Python floats holding fp32 values."""
     one = torch.tensor(1.0, dtype=torch.float32)
     pw1 = torch.tensor(b1 ** t, dtype=torch.float64).float()
@@ -251,7 +251,7 @@ def _reference(p, m, v, g, hp, t):
     gradient), with the hyper-parameters as the kernel receives them (rounded to float32; c1 and
     c2_sqrt from `_host_constants`), and per-element bounds on what fp32 may differ by.
 
-    Derivation, from `adamw()` in csrc/hip/xgmi_adam.hip with u = 2^-24. Every fp32 operation
+    Derivation, from `adamw()` in csrc/hip/xgmi_adam_device.h with u = 2^-24. Every fp32 operation
     returns its exact result times (1 + d); |d| <= u for +, -, * (an FMA contraction only
     removes roundings), and |d| <= 2u (one ulp, the documented maximum of the device's sqrtf
     and fp32 division) for sqrt and /. Terms of order u^2 are covered by the factor 1.01.
@@ -604,6 +604,69 @@ def test_state_access_modes_in_child_processes():
                            timeout=120, cwd=root, env=env)
         assert r.returncode == 0 and f"mode-ok {mode}" in r.stdout, (mode, r.returncode, r.stdout[-500:], r.stderr[-3000:])
         assert "MXAR_ADAM_STREAM ignored" not in r.stderr, r.stderr[-500:]  # the knob was honoured
+
+
+# ------------------------------------------------------------------------------------------
+# Which product of a moment update is rounded (moment() / grad_fused() in xgmi_adam_device.h)
+# ------------------------------------------------------------------------------------------
+def _grad_fused(plan, n, pack):
+    """Per element of a world-1 launch: True where adamw_unit forms fma(1 - beta, g, fl(beta s)),
+    False where it forms fma(beta, s, fl((1 - beta) g)): elements x, y of the float4s of a lane's
+    second pack (pack index i of the unit with (i // 256) odd) under plain state loads, and the
+    scalar tail. pack 8: the run-contiguous halves, where a run of `rows` packs holds the x..w of
+    lane l's half h at h * rows * 4 + l * 4."""
+    gf = torch.zeros(n, dtype=torch.bool)
+    for c in range(plan["nch"]):
+        clen = max(0, min(n - c * plan["chunk"], plan["chunk"]))
+        for q in range(plan["sub"]):
+            ulen = max(0, min(clen - q * plan["subchunk"], plan["subchunk"]))
+            start = c * plan["chunk"] + q * plan["subchunk"]
+            npk = ulen // pack
+            j = torch.arange(npk * pack)
+            if pack == 4:
+                w, k = (j // 4 // 256) % 2, j % 4
+            else:
+                run = j // 2048
+                rows = torch.clamp(npk - run * 256, max=256)
+                w, k = run % 2, ((j - run * 2048) % (rows * 4)) % 4
+            gf[start:start + npk * pack] = ~((w == 1) & (k < 2))
+    return gf
+
+
+@gpu
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_moment_roundings_are_the_pinned_ones(dtype):
+    """beta1 = beta2 = 0.75, so (1 - beta) g = g / 4 is exact and the two candidates of each moment
+    are computable exactly in float64 (every value is a multiple of 2^-30 at least, below 2; g^2 / 4
+    a multiple of 2^-16): fl(0.75 s + g / 4) with one rounding where the gradient's product is the
+    rounded one, fl(fl(0.75 s) + g / 4) where the state's is; for the second moment t = fl(g^2 / 4)
+    and fl(0.75 v + t) against fl(g^2 / 4 + fl(0.75 v)). The moments must have the bits of the
+    candidate that grad_fused() names for the element's place, and the candidates must differ
+    often enough for that to say something."""
+    cl = _cluster(1)
+    n, es = NMAX, _es(dtype)
+    gen = torch.Generator().manual_seed(4242)
+    m = torch.randint(-(2 ** 24) + 1, 2 ** 24, (n,), generator=gen).double() * 2.0 ** -24
+    v = torch.randint(0, 2 ** 24, (n,), generator=gen).double() * 2.0 ** -28  # below g^2 / 4 often: two roundings show
+    g = torch.randint(2, 128, (n,), generator=gen).double() * 2.0 ** -7 * (torch.randint(0, 2, (n,), generator=gen) * 2 - 1)
+    assert torch.equal(g.to(dtype).double(), g) and torch.equal(m.float().double(), m)
+    case = _make_case(cl, n, dtype, torch.zeros(n), m.float(), v.float())
+    cl.step_adamw([g.to(dtype).to(DEV)], case["params"], case["states"], step=1, lr=1e-2, betas=(0.75, 0.75), eps=1e-8,
+                  weight_decay=0.0)
+    cl.check()
+    f32 = lambda x: x.float().double()
+    gf = _grad_fused(H.plan_allreduce("adamw", cl.comms[0].knobs, n, es, 1), n, 16 // es)
+    assert 0.7 < gf.float().mean() < 0.9  # all but x, y of every other run of 256 packs, and the tails
+    for key, grad_rounded, state_rounded in (
+            ("exp_avg", (0.75 * m + g / 4).float(), (f32(0.75 * m) + g / 4).float()),
+            ("exp_avg_sq", (0.75 * v + f32(g * g / 4)).float(), (g * g / 4 + f32(0.75 * v)).float())):
+        assert (grad_rounded != state_rounded).float().mean() > 0.01, key
+        want = torch.where(gf, state_rounded, grad_rounded)
+        got = _gather(case, key).cpu()
+        print(f"{key} {dtype}: {int((got != want).sum())} of {n} differ from the pinned candidate; "
+              f"{int((got != grad_rounded).sum())} from 'gradient product rounded' everywhere, "
+              f"{int((got != state_rounded).sum())} from 'state product rounded' everywhere")
+        assert torch.equal(got, want), f"{key}: {_first_diff(got, want)}"
 
 
 # ------------------------------------------------------------------------------------------

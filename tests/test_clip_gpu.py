@@ -267,11 +267,11 @@ def test_update_half_equals_the_fused_step_bit_for_bit(P, dtype):
     narrow grid: multiples of 2^-10 below 2^-2 in bf16, 2 in fp16; 2^-13 at least after the
     coefficient, far above the smallest fp16 subnormal 2^-24). Everything after it is adamw().
 
-    The two kernels are compiled separately and the compiler orders and contracts the products
-    of adamw() by the code around them (fma(beta1, m, (1 - beta1) g) or fma(1 - beta1, g, beta1 m),
-    differently even between the elements of one pack), so this holds only because the update
-    kernel carries the fused kernel's unit body as the same text in the same place; the figures
-    are printed for the day it stops holding."""
+    The two kernels are compiled separately; both run the one adamw_unit of
+    csrc/hip/xgmi_adam_device.h, whose moment() fixes which product of a moment update is rounded
+    (fma(beta1, m, fl((1 - beta1) g)) or fma(1 - beta1, g, fl(beta1 m)), by the element's place),
+    and differ only in the gradient source (the P-way sum or the fp32 shard), which this test
+    holds against each other; the figures are printed for the day it stops holding."""
     cl = A._cluster(P)
     cpu, xs = A._data(P, dtype, mode="narrow")
     before = (cl.comms[0].stats.rs_sq, cl.comms[0].stats.adamw_shard)

@@ -2,21 +2,34 @@
 """What gradient clipping costs the fused sharded-DP step: P logical ranks on ONE MI355X, n
 parameters in one bucket (default 8 ranks x 134 M bf16, the size of profiles/round4).
 
-Three step times, alternating in one call:
+Step times, alternating in one call:
   clipped   reduce_scatter_sq + clip_coef + step_adamw_shard of this tree
   fused     step_adamw of this tree
-  parent    step_adamw of another checkout (--parent PATH, built there), in child processes
-            started between this tree's rounds
+  parent, parent_clipped
+            the same two of another checkout (--parent PATH, built there), in child processes
+            started between this tree's rounds. The child is THIS file run on that checkout's
+            package, so the checkout needs this tree's Python API (reduce_scatter_sq with
+            `accumulate`, clip_coef, step_adamw_shard); an older one fails in the child.
 
 Every round times `iters` steps of each variant in turn with device events; the figure of a
 variant is the median over rounds of the round's median. Byte model per owned parameter: fused
-14 B read + 14 B written, clipped 8 B more (the fp32 shard written and read once).
+14 B read + 14 B written, clipped 8 B more (the fp32 shard written and read once). With
+--parent the summary also holds `margin`: the relative spread (max - min over median) of the
+parent's own round medians, and `within_margin`: this tree's median <= parent's * (1 + margin).
 
     python tools/clip_step_cost.py --parent ab_old --out profiles/clip_step.json
+
+--digest (with --parent): no timing. The fused step, the clipped step and the accumulating
+clipped step (two micro-batches, then the update) run three chained steps each on small seeded
+cases - P in {1, 2, 3, 8}, fp32 / bf16 / fp16, n in {4099, 65 539, 300 003}, 2 MiB slots,
+grid 64 - here and in a child on the parent's package; one SHA-256 per case over every rank's
+parameters, master, moments, gradient shard and sum of squares. Exit status 1 if a digest
+differs from the parent's (2: the child failed).
 """
 from __future__ import annotations
 
 import argparse
+import hashlib
 import json
 import os
 import statistics
@@ -84,6 +97,61 @@ def measure(args, variants):
     return out
 
 
+def digests():
+    """{case: SHA-256} of the three step forms with the package that is first on sys.path."""
+    import torch
+
+    from akka_allreduce_1_amd.ops import dtype_code, fill_uniform
+    from akka_allreduce_1_amd.parallel import LocalCluster
+
+    dev = torch.device("cuda", 0)
+    out = {}
+    for P in (1, 2, 3, 8):  # 3: the runtime-P loops
+        cl = LocalCluster(P, slot_bytes=2 << 20, grid=64, timeout_s=20)
+        for name, dtype in (("fp32", torch.float32), ("bf16", torch.bfloat16), ("fp16", torch.float16)):
+            for n in (4099, 65_539, 300_003):
+                b = cl.comms[0].block_elems(n, dtype_code(dtype))
+                full = fill_uniform(torch.empty(n, device=dev), seed=1)
+                for form in ("fused", "clipped", "accum"):
+                    params = [full.to(dtype, copy=True) for _ in range(P)]
+                    states = []
+                    for k in range(P):
+                        own = full[k * b:(k + 1) * b]
+                        st = {key: torch.zeros(b, device=dev) for key in ("master", "exp_avg", "exp_avg_sq")}
+                        st["master"][:own.numel()] = own
+                        states.append(st)
+                    gshards = [torch.zeros(b, device=dev) for _ in range(P)]
+                    sha = hashlib.sha256()
+                    for step in (1, 2, 3):
+                        micro = [[fill_uniform(torch.empty(n, dtype=dtype, device=dev), seed=1000 * step + 100 * m + k)
+                                  for k in range(P)] for m in range(2)]
+                        sqs = []
+                        if form == "fused":
+                            cl.step_adamw(micro[0], params, states, step=step, **HP)
+                        else:
+                            sqs = cl.reduce_scatter_sq(micro[0], gshards)
+                            if form == "accum":
+                                sqs = cl.reduce_scatter_sq(micro[1], gshards, accumulate=True)
+                            _, coef = cl.clip_coef(sqs, 1.0)
+                            cl.step_adamw_shard(gshards, params, states, coef=coef, step=step, **HP)
+                        cl.check()
+                        for k in range(P):
+                            for t in [params[k], *states[k].values(), gshards[k], *sqs[k:k + 1]]:
+                                sha.update(t.reshape(-1).view(torch.uint8).cpu().numpy().tobytes())
+                    out[f"P{P} {name} n{n} {form}"] = sha.hexdigest()
+    return out
+
+
+def _child(tree, extra):
+    """This file run on the package of the checkout `tree`; the last line of its output."""
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"] + extra, capture_output=True, text=True,
+                       timeout=600, cwd=tree, env=dict(os.environ, PYTHONPATH=tree, MXAR_CLIP_COST_TREE=tree))
+    if r.returncode != 0:
+        print(r.stderr[-2000:], file=sys.stderr)
+        return None
+    return json.loads(r.stdout.strip().splitlines()[-1])
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--ranks", type=int, default=8)
@@ -93,33 +161,46 @@ def main() -> int:
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--parent", default=None, help="another built checkout whose fused step is timed too")
+    ap.add_argument("--parent", default=None, help="another built checkout (with this tree's Python API) whose steps are timed or digested too")
+    ap.add_argument("--digest", action="store_true", help="compare result digests with --parent instead of timing")
     ap.add_argument("--out", default=None)
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
-    if args.child:  # the fused step of the checkout on PYTHONPATH, one round set
-        print(json.dumps(measure(args, ["fused"])), flush=True)
+    if args.child:  # the checkout on PYTHONPATH: its digests, or one round set of its two steps
+        print(json.dumps(digests() if args.digest else measure(args, ["clipped", "fused"])), flush=True)
         return 0
-    res = {"clipped": [], "fused": [], "parent": []}
+    if args.digest:
+        if not args.parent:
+            ap.error("--digest needs --parent")
+        here = digests()
+        there = _child(os.path.abspath(args.parent), ["--digest"])
+        if there is None:
+            return 2
+        differ = sorted(c for c in here if here[c] != there.get(c))
+        for c in sorted(here):
+            print(("DIFFERS " if c in differ else "same    ") + c + " " + here[c], flush=True)
+        summary = {"cases": len(here), "differ": differ,
+                   "all": hashlib.sha256("".join(here[c] for c in sorted(here)).encode()).hexdigest()}
+        print(json.dumps(summary), flush=True)
+        if args.out:
+            with open(args.out, "w") as f:
+                json.dump(dict(summary, here=here, parent=there), f, indent=1)
+        return 1 if differ or len(there) != len(here) else 0
+    res = {"clipped": [], "fused": [], "parent": [], "parent_clipped": []}
     passes = 3 if args.parent else 1
     for _ in range(passes):  # this tree and the parent take turns
         here = measure(args, ["clipped", "fused"])
         res["clipped"] += here["clipped"]
         res["fused"] += here["fused"]
         if args.parent:
-            tree = os.path.abspath(args.parent)
-            cmd = [sys.executable, os.path.join(tree, "tools", "clip_step_cost.py")]
-            if not os.path.exists(cmd[1]):  # the parent has no such tool: this file, its package
-                cmd = [sys.executable, os.path.abspath(__file__)]
-            cmd += ["--child", "--ranks", str(args.ranks), "--n", str(args.n), "--dtype", args.dtype, "--grid",
-                    str(args.grid), "--iters", str(args.iters), "--warmup", str(args.warmup), "--rounds",
-                    str(args.rounds)]
-            r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=tree,
-                               env=dict(os.environ, PYTHONPATH=tree, MXAR_CLIP_COST_TREE=tree))
-            if r.returncode != 0:
-                print(r.stderr[-2000:], file=sys.stderr)
-                return 1
-            res["parent"] += json.loads(r.stdout.strip().splitlines()[-1])["fused"]
+            there = _child(os.path.abspath(args.parent),
+                           ["--ranks", str(args.ranks), "--n", str(args.n), "--dtype", args.dtype, "--grid",
+                            str(args.grid), "--iters", str(args.iters), "--warmup", str(args.warmup), "--rounds",
+                            str(args.rounds)])
+            if there is None:
+                return 2
+            res["parent"] += there["fused"]
+            res["parent_clipped"] += there["clipped"]
     med = {k: round(statistics.median(v), 4) for k, v in res.items() if v}
     es = 2 if args.dtype == "bf16" else 4
     owned = args.n  # all ranks live on this device: every parameter is owned here once
@@ -128,6 +209,11 @@ def main() -> int:
                "clipped_over_fused": round(med["clipped"] / med["fused"], 4),
                "byte_model": {"fused_B_per_param": 28, "clipped_B_per_param": 36, "ratio": round(36 / 28, 4),
                               "elem_size": es, "owned_params_on_device": owned}}
+    if args.parent:
+        pairs = {"fused": "parent", "clipped": "parent_clipped"}
+        margin = {v: (max(res[p]) - min(res[p])) / statistics.median(res[p]) for v, p in pairs.items()}
+        summary["margin"] = {v: round(m, 4) for v, m in margin.items()}
+        summary["within_margin"] = {v: med[v] <= med[p] * (1 + margin[v]) for v, p in pairs.items()}
     print(json.dumps(summary), flush=True)
     if args.out:
         with open(args.out, "w") as f:
