@@ -157,6 +157,27 @@ def gather_sq_records(comm, rec: torch.Tensor) -> torch.Tensor:
     return out.view(torch.float64).view(comm.world, 2)
 
 
+def _check_scale_buffers(state: torch.Tensor, record: torch.Tensor, device) -> None:
+    if state.dtype != torch.int32 or state.numel() != 4 or not state.is_contiguous() or state.device != device:
+        raise ValueError(f"loss-scale state must be a contiguous int32 [4] tensor on {device}")
+    if record.dtype != torch.float32 or record.numel() != 8 or not record.is_contiguous() or record.device != device:
+        raise ValueError(f"step record must be a contiguous fp32 [8] tensor on {device}")
+
+
+def _launch_scale_step(dev_index: int, recs: torch.Tensor, world: int, state: torch.Tensor, record: torch.Tensor,
+                       table, cfg, max_norm) -> None:
+    """The step-control kernel (csrc/hip/xgmi_scale.hip) on the current stream of `dev_index`.
+    recs: the gathered 16-byte records, world x 2 float64 however viewed."""
+    if recs.numel() * recs.element_size() != 16 * world or not recs.is_contiguous():
+        raise ValueError("one contiguous 16-byte record per rank")
+    if table.filled < 1 or table.tensor.device != state.device:
+        raise ValueError("the correction table must be filled (CorrectionTable.ensure) on the state's device")
+    _H.scale_step(dev_index, _current_stream(dev_index), recs.data_ptr(), world, state.data_ptr(), record.data_ptr(),
+                  table.tensor.data_ptr(), table.end, table.filled, max_norm is not None,
+                  0.0 if max_norm is None else float(max_norm), bool(cfg.dynamic), cfg.growth_factor,
+                  cfg.backoff_factor, cfg.growth_interval)
+
+
 class XgmiCommunicator:
     """Allreduce over directly mapped peer HBM for the ranks of a torch.distributed group."""
 
@@ -713,6 +734,39 @@ class XgmiCommunicator:
                                  state["exp_avg"].data_ptr(), state["exp_avg_sq"].data_ptr(), h)
         return params
 
+    # -------------------------------------------- the loss-scaled step (csrc/hip/xgmi_scale.hip)
+    def loss_scale_step(self, sqs, state: torch.Tensor, record: torch.Tensor, table, cfg,
+                        max_norm: float | None = None) -> None:
+        """Between the halves of a loss-scaled split step: all-gather one 16-byte record per rank
+        (as `clip_coef` does) and launch the one-wave control kernel on them. It evaluates
+        `loss_scale.scale_step_rule` on the device - same bits on every rank - updates `state`
+        (int32 [4]: scale bits, tracker, applied, skipped) in place and writes `record` (fp32 [8]:
+        coef, skip word, c1, c2_sqrt, norm, clip) for `step_adamw_record`. `table`: a
+        `loss_scale.CorrectionTable`, filled by the caller past the count this step can reach.
+        Replaces the P + 4 small torch launches of `clip_coef_from_records`. No host sync."""
+        _check_scale_buffers(state, record, self.device)
+        recs = gather_sq_records(self, sq_record(sqs))
+        _launch_scale_step(self._dev, recs, self.world, state, record, table, cfg, max_norm)
+
+    def step_adamw_record(self, gshard: torch.Tensor, params: torch.Tensor, state: dict, *, record: torch.Tensor,
+                          lr: float, betas: tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
+                          weight_decay: float = 0.0, grid: int = 0) -> torch.Tensor:
+        """`step_adamw_shard` driven by the step record `loss_scale_step` left: coefficient and bias
+        corrections come from it, and when its skip word is set the launch writes nothing - not
+        the shard state, not `params`, not a peer's slot - while it still takes part in the flag
+        protocol (csrc/hip/xgmi_clip.hip), so any launch may follow on every rank."""
+        if record.dtype != torch.float32 or record.numel() != 8 or record.get_device() != self._dev:
+            raise ValueError(f"record must be an 8-element fp32 tensor on {self.device}")
+        if gshard.dtype != torch.float32 or gshard.numel() != self.shard_len(params.numel(), params.dtype):
+            raise ValueError("gshard must hold shard_len(n) fp32 elements")
+        self._step_grid(grid)
+        h = _H.AdamW()
+        h.lr, (h.beta1, h.beta2), h.eps, h.weight_decay, h.step = lr, betas, eps, weight_decay, 1
+        self._c.step_adamw_shard(gshard.data_ptr(), record.data_ptr(), params.data_ptr(), params.numel(),
+                                 _dtype_code(params.dtype), _current_stream(self._dev), state["master"].data_ptr(),
+                                 state["exp_avg"].data_ptr(), state["exp_avg_sq"].data_ptr(), h, record=True)
+        return params
+
     def shard_len(self, n: int, dtype: torch.dtype) -> int:
         """Elements of the block a rank owns in a fused step over n elements."""
         return self._c.block_elems(n, _dtype_code(dtype))
@@ -1041,6 +1095,42 @@ class LocalCluster:
                 [params[k].data_ptr() for k in g], n, code, torch.cuda.current_stream(dev).cuda_stream,
                 [(states[k]["master"].data_ptr(), states[k]["exp_avg"].data_ptr(), states[k]["exp_avg_sq"].data_ptr())
                  for k in g], h)
+
+    def loss_scale_step(self, sqs: Sequence, states: Sequence[torch.Tensor], records: Sequence[torch.Tensor],
+                        tables: Sequence, cfg, max_norm: float | None = None) -> None:
+        """The control kernel of the loss-scaled step for every logical rank, each on its own
+        state, record and table (see XgmiCommunicator.loss_scale_step)."""
+        recs = [sq_record(s) for s in sqs]
+        if self.world == 1:
+            outs = recs
+        else:
+            outs = self.collective("all_gather", [r.view(torch.float32) for r in recs])
+        for k in range(self.world):
+            _check_scale_buffers(states[k], records[k], self.devices[k])
+            with torch.cuda.device(self.devices[k]):
+                _launch_scale_step(self.devices[k].index, outs[k], self.world, states[k], records[k], tables[k], cfg,
+                                   max_norm)
+
+    def step_adamw_record(self, gshards: Sequence[torch.Tensor], params: Sequence[torch.Tensor],
+                          states: Sequence[dict], *, records: Sequence[torch.Tensor], lr: float,
+                          betas: tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
+                          weight_decay: float = 0.0) -> None:
+        """The record-driven update half for every logical rank; records[k]: rank k's step record."""
+        h = _H.AdamW()
+        h.lr, (h.beta1, h.beta2), h.eps, h.weight_decay, h.step = lr, betas, eps, weight_decay, 1
+        n = params[0].numel()
+        code = _dtype_code(params[0].dtype)
+        self._check_shards(params, gshards, n, code)
+        for k in range(self.world):
+            if records[k].dtype != torch.float32 or records[k].numel() != 8 or records[k].device != self.devices[k]:
+                raise ValueError(f"rank {k}: record must be an 8-element fp32 tensor on {self.devices[k]}")
+        for g in self.groups:
+            dev = self.devices[g[0]]
+            _H.XgmiComm.step_adamw_shard_local(
+                [self.comms[k] for k in g], [gshards[k].data_ptr() for k in g], [records[k].data_ptr() for k in g],
+                [params[k].data_ptr() for k in g], n, code, torch.cuda.current_stream(dev).cuda_stream,
+                [(states[k]["master"].data_ptr(), states[k]["exp_avg"].data_ptr(), states[k]["exp_avg_sq"].data_ptr())
+                 for k in g], h, record=True)
 
     def barrier(self) -> None:
         for g in self.groups:

@@ -65,6 +65,41 @@ accumulator per bucket the size of `grad_shard`; at `step()` `grad_shard` receiv
 rounded once. Norm and coefficient are those of the accumulated gradient. `accumulate()` zeroes
 the flat gradients itself; `zero_grad()` stays a between-steps call. Accumulators are scratch:
 `state_dict()` raises between `accumulate()` and `step()`. Not with `step_in_backward`.
+
+`loss_scale=` makes fp16 parameters trainable and makes a non-finite gradient harmless in every
+element type: `loss_scale=<float>` is a static scale (`1.0`: only skip non-finite steps, the bf16
+use), `loss_scale={"init_scale": 65536.0, "growth_factor": 2.0, "backoff_factor": 0.5,
+"growth_interval": 2000}` a dynamic one (all keys optional, these are the defaults - those of
+`torch.amp.GradScaler`, which cannot work here: `p.grad` is a view of the un-reduced flat gradient
+and the fused path owns the optimizer), `loss_scale=True` dynamic with the defaults. Call
+`zdp.scale_loss(loss).backward()` (one device multiply, no sync), then `step()` as ever. The step
+is decided where the clipped step takes its norm: the ranks' sums of squares of the reduced
+gradient are added in rank order, and the total is non-finite exactly when some reduced element
+is. Then the step is skipped - parameters, optimizer state and the step count AdamW's bias
+corrections use stay as they were, on every rank alike - and a dynamic scale backs off; otherwise
+the gradient is multiplied by coef = clip / scale (rounded once) and the scale grows after
+`growth_interval` clean steps. The rule is `loss_scale.scale_step_rule`. `loss_scale` (0-d fp32),
+`last_step_skipped` (0-d integer), `skipped_steps` and `applied_steps` (counters; `applied_steps`
+is AdamW's t) are device tensors; `last_grad_norm` is the norm of the UNSCALED gradient (inf or
+NaN on a skipped step), `last_clip_coef` the clip coefficient; `stats["steps"]` keeps counting
+`step()` calls. Works with `max_grad_norm`, with `grad_accumulation` (the scale changes only in
+`step()`: every micro-batch of a step is scaled alike, and a non-finite value in any of them reaches
+the accumulated shard and so the sum of squares), with both and with neither; not with
+`step_in_backward` (the update would precede the decision). Fused: `loss_scale` forces the split
+step, as `max_grad_norm` does - the one-launch `step_adamw` cannot know the decision before it
+updates. Between the halves ONE one-wave launch (csrc/hip/xgmi_scale.hip) evaluates the rule on
+the gathered records, updates scale and counters in place and writes a step record; every
+bucket's update half reads coefficient, bias corrections and skip word from it, and a skipped
+launch writes nothing. No host sync: `last_grad_norm`, `last_clip_coef` and `last_step_skipped` are
+then views of that record, valid until the next `step()`. Unfused: the same rule in torch ops, and
+ONE host sync per step (a `bool()` of the found flag) - torch optimizers have no device-side skip,
+as `GradScaler` documents for non-fused optimizers. `state_dict()` gains `"loss_scale": {"scale",
+"growth_tracker", "skipped"}` and its `"step"` is the applied count (reading them is one sync, at a
+checkpoint); a checkpoint without the key loads into a loss-scaled instance (the configured initial
+scale, every saved step applied), and one written without `loss_scale=` loads as it always did.
+Limits: the decision is taken on the sum of squares, so a finite gradient whose squares overflow
+fp32 is treated as an overflow - skipped, the scale backs off: conservative, and it corrects
+itself; found flag and coefficient are per step over all buckets, not per bucket.
 """
 from __future__ import annotations
 
@@ -72,6 +107,7 @@ from typing import Callable, Iterable
 
 import torch
 
+from . import loss_scale as _ls
 from .comm import clip_coef_from_records, comm_stream, gather_sq_records, sq_record
 
 _ALIGN_BYTES = 16
@@ -97,7 +133,7 @@ class ShardedDataParallel:
                  optimizer_factory: Callable[[list[torch.nn.Parameter]], torch.optim.Optimizer] | None, *,
                  bucket_bytes: int = 64 << 20, overlap: bool = True, fused_adamw: dict | None = None,
                  step_in_backward: bool = False, comm_grid: int = 0, max_grad_norm: float | None = None,
-                 grad_accumulation: bool = False):
+                 grad_accumulation: bool = False, loss_scale: float | dict | bool | None = None):
         params = module.parameters() if isinstance(module, torch.nn.Module) else module
         self.params = [p for p in params if p.requires_grad]
         if not self.params:
@@ -111,6 +147,10 @@ class ShardedDataParallel:
             raise ValueError("max_grad_norm cannot be combined with step_in_backward: the update of a bucket "
                              "would precede the norm over gradients that do not exist yet")
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        if loss_scale is not None and step_in_backward:
+            raise ValueError("loss_scale cannot be combined with step_in_backward: the update of a bucket would "
+                             "precede the decision whether the step is skipped")
+        self._scale_cfg = None if loss_scale is None else _ls.LossScaleConfig(loss_scale)
         self.comm = comm
         self.world = int(getattr(comm, "world"))
         self.rank = int(getattr(comm, "rank"))
@@ -121,6 +161,8 @@ class ShardedDataParallel:
         self.buckets = self._build(bucket_bytes)
         self.slot_of = {id(p): (b, off) for b in self.buckets for p, off in zip(b.params, b.offsets)}
         self.fused = dict(fused_adamw) if fused_adamw is not None else None
+        # the fused step is split where a global decision has to be known before any parameter moves
+        self._split = self.max_grad_norm is not None or self._scale_cfg is not None
         if self.fused is not None:
             self.fused["grid"] = int(comm_grid)
         self.adamw_states: list[dict] = []
@@ -135,12 +177,12 @@ class ShardedDataParallel:
             self.adamw_states = [comm.adamw_state(b.flat_param) for b in self.buckets]
             # without step_in_backward the fused launch runs in step(); with it, from the hooks.
             # Clipped: the reduce-scatter half may run from the hooks, the update half in step()
-            if self.max_grad_norm is None:
+            if not self._split:
                 self.overlap = bool(step_in_backward) and self.on_gpu
-            if self.max_grad_norm is not None or self.grad_accumulation:
+            if self._split or self.grad_accumulation:
                 if not hasattr(comm, "step_adamw_shard"):
-                    raise ValueError("fused_adamw with max_grad_norm or grad_accumulation needs a communicator "
-                                     "with step_adamw_shard")
+                    raise ValueError("fused_adamw with max_grad_norm, grad_accumulation or loss_scale needs a "
+                                     "communicator with step_adamw_shard")
                 # scratch, not in state_dict(): the fp32 gradient shard, also the accumulator over micro-batches
                 self.gshards = [comm.gshard(b.flat_param) for b in self.buckets]
                 self._sqs = [None] * len(self.buckets)
@@ -153,9 +195,11 @@ class ShardedDataParallel:
             if self.grad_accumulation:  # scratch, not in state_dict(): fp32 sums over micro-batches
                 self._accs = [torch.zeros(b.grad_shard.numel(), dtype=torch.float32, device=self.device)
                               for b in self.buckets]
-        self.step_in_backward = self.fused is not None and self.overlap and self.max_grad_norm is None
+        self.step_in_backward = self.fused is not None and self.overlap and not self._split
         self.last_grad_norm = torch.zeros((), dtype=torch.float32, device=self.device)
         self.last_clip_coef = torch.ones((), dtype=torch.float32, device=self.device)
+        if self._scale_cfg is not None:
+            self._init_loss_scale()
         self._t_started = False
         self._hooks = [p.register_post_accumulate_grad_hook(self._on_grad) for p in self.params]
         self._next = 0
@@ -251,7 +295,7 @@ class ShardedDataParallel:
     def _reduce(self, b: _Bucket) -> None:
         if self.fused is not None:
             # grad_accumulation, unclipped: only accumulate() and a step() that follows one get here
-            if self.max_grad_norm is not None or self.grad_accumulation:
+            if self._split or self.grad_accumulation:
                 self._rs_sq_bucket(b)
             else:
                 self._fused_bucket(b)
@@ -276,11 +320,17 @@ class ShardedDataParallel:
             self._t_started = False
             self.stats["steps"] += 1
             return
-        if self.fused is not None and (self.max_grad_norm is not None or self.micro_batches > 0):
-            # the split step: clipped, or the last micro-batch of an accumulated step
+        if self.fused is not None and (self._split or self.micro_batches > 0):
+            # the split step: clipped, loss-scaled, or the last micro-batch of an accumulated step
             self._launch_ready(all_=True)
             if self.overlap:
                 torch.cuda.current_stream(self.device).wait_stream(self.stream)
+            if self._scale_cfg is not None:
+                self._scaled_update_halves()
+                self._rearm()
+                self.micro_batches = 0
+                self.stats["steps"] += 1
+                return
             if self.max_grad_norm is not None:
                 self.last_grad_norm, self.last_clip_coef = self.comm.clip_coef(self._sqs, self.max_grad_norm)
                 coef = self.last_clip_coef
@@ -309,7 +359,13 @@ class ShardedDataParallel:
             torch.cuda.current_stream(self.device).wait_stream(self.stream)
         if self.micro_batches > 0:
             self._add_shards()
-        if self.max_grad_norm is not None:
+        if self._scale_cfg is not None:
+            if self._unscale_shards():  # the one host sync of the unfused path: torch optimizers cannot skip on the device
+                self._rearm()
+                self.micro_batches = 0
+                self.stats["steps"] += 1
+                return
+        elif self.max_grad_norm is not None:
             self._clip_shards()
         elif self.micro_batches > 0:
             for b, acc in zip(self.buckets, self._accs):
@@ -373,6 +429,63 @@ class ShardedDataParallel:
             else:
                 b.grad_shard.mul_(self.last_clip_coef)
 
+    # ------------------------------------------------------------------ loss scaling
+    def _init_loss_scale(self) -> None:
+        cfg = self._scale_cfg
+        self._scale_state = _ls.new_state(cfg, self.device)  # int32 [4]: scale bits, tracker, applied, skipped
+        self.loss_scale = _ls.scale_of(self._scale_state)
+        self.applied_steps = self._scale_state[_ls.APPLIED]
+        self.skipped_steps = self._scale_state[_ls.SKIPPED]
+        self.last_step_skipped = torch.zeros((), dtype=torch.int32, device=self.device)
+        self._applied_bound = 0  # host side: the applied count is at most this (no sync)
+        if self.fused is not None:
+            if not hasattr(self.comm, "step_adamw_record"):
+                raise ValueError("fused_adamw with loss_scale needs a communicator with step_adamw_record")
+            self._record = torch.zeros(_ls.REC_WORDS, dtype=torch.float32, device=self.device)
+            self._record[_ls.REC_COEF] = 1.0
+            self._table = _ls.CorrectionTable(self.device, self.fused.get("betas", (0.9, 0.999)))
+            # views of the step record: what they show is the last step's until the next step() runs
+            self.last_step_skipped = self._record[_ls.REC_SKIP:_ls.REC_SKIP + 1].view(torch.int32)[0]
+            self.last_grad_norm = self._record[_ls.REC_NORM]
+            self.last_clip_coef = self._record[_ls.REC_CLIP]
+
+    def scale_loss(self, loss: torch.Tensor) -> torch.Tensor:
+        """loss * scale: one device multiply, no sync. Call backward() on the result."""
+        if self._scale_cfg is None:
+            raise RuntimeError("scale_loss() needs ShardedDataParallel(..., loss_scale=...)")
+        return loss * self.loss_scale
+
+    def _scaled_update_halves(self) -> None:
+        """Fused, loss-scaled: the control kernel on the gathered sums of squares, then every
+        bucket's record-driven update half (a skipped one writes nothing)."""
+        self._applied_bound += 1
+        self._table.ensure(self._applied_bound)
+        self.comm.loss_scale_step(self._sqs, self._scale_state, self._record, self._table, self._scale_cfg,
+                                  self.max_grad_norm)
+        for b, st, gs in zip(self.buckets, self.adamw_states, self.gshards):
+            self.comm.step_adamw_record(gs, b.flat_param, st, record=self._record, **self.fused)
+            self.stats["all_gather_bytes"] += b.flat_param.numel() * b.flat_param.element_size()
+            self.stats["clip_bytes"] += 8 * gs.numel()
+
+    def _unscale_shards(self) -> bool:
+        """Unfused, loss-scaled: the sums of squares as `_clip_shards` takes them, the rule
+        (loss_scale.scale_step_rule), and - unless the step is skipped - every shard times
+        coef = clip / scale, rounded once. Returns whether the step is skipped (one host sync)."""
+        srcs = self._accs if self.micro_batches > 0 else [b.grad_shard.float() for b in self.buckets]
+        sqs = [s.pow(2).sum() for s in srcs]
+        recs = gather_sq_records(self.comm, sq_record(sqs))
+        self.last_grad_norm, self.last_clip_coef, coef, found = _ls.scale_step_rule(
+            recs, self._scale_state, self._scale_cfg, self.max_grad_norm)
+        self.last_step_skipped = found.to(torch.int32)
+        if bool(found):
+            return True
+        for b, s in zip(self.buckets, srcs):
+            if self.micro_batches > 0:
+                b.grad_shard.copy_(s * coef)
+            else:
+                b.grad_shard.mul_(coef)
+        return False
+
     # ------------------------------------------------------------------ checkpoint / resume
     def state_dict(self) -> dict:
         """This rank's shard of the optimizer state, for resume (the reference
@@ -385,6 +498,10 @@ class ShardedDataParallel:
                                "are held in accumulators, which are scratch and never checkpointed")
         sd = {"world": self.world, "rank": self.rank, "step": self._t, "steps": self.stats["steps"],
               "layout": [[b.numel, str(b.dtype), len(b.params)] for b in self.buckets]}
+        if self._scale_cfg is not None:  # one sync, at a checkpoint
+            _, tracker, applied, skipped = self._scale_state.tolist()
+            sd["step"] = applied
+            sd["loss_scale"] = {"scale": float(self.loss_scale), "growth_tracker": tracker, "skipped": skipped}
         if self.fused is not None:
             sd["adamw"] = [{k: st[k] for k in ("master", "exp_avg", "exp_avg_sq")} for st in self.adamw_states]
         else:
@@ -413,6 +530,16 @@ class ShardedDataParallel:
             self.optimizer.load_state_dict(sd["optimizer"])
         self._t = int(sd["step"])
         self.stats["steps"] = int(sd["steps"])
+        if self._scale_cfg is not None:
+            # a checkpoint of a run without loss scaling: the configured initial scale, every step of it applied
+            # (an unfused one counts them in "steps" alone: its optimizer keeps AdamW's own count)
+            saved = sd.get("loss_scale", {"scale": self._scale_cfg.init_scale, "growth_tracker": 0, "skipped": 0})
+            if "loss_scale" not in sd and self.fused is None:
+                self._t = int(sd["steps"])
+            fresh = torch.tensor([0, int(saved["growth_tracker"]), self._t, int(saved["skipped"])], dtype=torch.int32)
+            fresh[:1].view(torch.float32).fill_(float(saved["scale"]))
+            self._scale_state.copy_(fresh)
+            self._applied_bound = self._t
 
     def zero_grad(self) -> None:
         for b in self.buckets:

@@ -166,6 +166,44 @@ struct CommArgs {
   const float* coef[kMaxRanks];
 };
 
+// Loss-scaled step (xgmi_scale.hip). The step record: what the one-wave step-control kernel
+// decides between the two halves of the split step and the record-driven update half
+// (xgmi_clip.hip) reads instead of CommArgs::coef / c1 / c2_sqrt. 32 bytes, 16-byte aligned, one
+// per rank, in ordinary device memory; `coef` comes first, so CommArgs::coef[y] points at it.
+struct StepRecord {
+  float coef;      // clip / scale: what the update half multiplies the fp32 shard by
+  uint32_t skip;   // 1: a non-finite sum of squares - the update half writes nothing
+  float c1;        // AdamW's bias corrections at the applied count, from the host's table
+  float c2_sqrt;
+  float norm;      // the norm of the unscaled gradient
+  float clip;      // min(1, max_norm / (norm + 1e-6)), 1.0f when not clipping
+  uint32_t short_table;  // 1: the applied count passed the filled part of the table (a host bug)
+  uint32_t pad;
+};
+static_assert(sizeof(StepRecord) == 32 && offsetof(StepRecord, coef) == 0, "the step record is read by offset");
+// The scaler's device state, updated in place by the control kernel: four 32-bit words.
+struct ScaleState {
+  float scale;
+  int32_t tracker;  // clean steps since the scale last changed
+  int32_t applied;  // steps that updated the parameters: AdamW's t
+  int32_t skipped;
+};
+static_assert(sizeof(ScaleState) == 16, "the scaler state is viewed as four words");
+struct ScaleStepArgs {
+  const double* recs;  // [P][2]: the ranks' 16-byte records in rank order, [k][0] = sum of squares
+  int P;
+  int clip;            // 0: clip = 1.0f
+  float max_norm;
+  int dynamic;         // 0: a static scale
+  float growth, backoff;
+  int interval;
+  ScaleState* state;
+  StepRecord* rec;
+  const float* table;  // (c1, c2_sqrt) of count t at [2 (t - 1)], t = 1 .. filled
+  int end;             // the count from which both corrections are 1.0f: the index clamps there
+  int filled;          // counts the host has filled so far (<= end)
+};
+
 // A plane group's resident kernel (threshold_group_resident_kernel): y = 0 is the dispatcher
 // row, y = 1 + k worker k's slice.
 struct GroupResArgs {

@@ -298,6 +298,43 @@ void bind_hip(py::module_& m) {
       },
       py::arg("kind"), py::arg("knobs"), py::arg("n"), py::arg("elem_size"), py::arg("ranks_here") = 1,
       "geometry of one allreduce segment of n elements: block, chunk, subchunk, nch, sub, sgroup, gx");
+  // the loss-scaled step (xgmi_scale.hip): the host's bias corrections, and the control kernel
+  h.def(
+      "adamw_corrections",
+      [](float beta1, float beta2, int first, int count) {
+        std::vector<float> out(2 * static_cast<size_t>(count > 0 ? count : 0));
+        for (int i = 0; i < count; ++i) adamw_corrections(beta1, beta2, first + i, &out[2 * i], &out[2 * i + 1]);
+        return out;
+      },
+      py::arg("beta1"), py::arg("beta2"), py::arg("first"), py::arg("count"),
+      "(c1, c2_sqrt) of steps first .. first + count - 1, flat, as the fused step's host code computes them");
+  h.def("adamw_corrections_end", &adamw_corrections_end, py::arg("beta1"), py::arg("beta2"), py::arg("cap"),
+        "the first step from which both corrections are exactly 1.0f, or cap");
+  h.def(
+      "scale_step",
+      [](int device, uintptr_t stream, uintptr_t recs, int world, uintptr_t state, uintptr_t record, uintptr_t table,
+         int table_end, int table_filled, bool clip, float max_norm, bool dynamic, float growth, float backoff,
+         int interval) {
+        ScaleStepArgs a{};
+        a.recs = reinterpret_cast<const double*>(recs);
+        a.P = world;
+        a.clip = clip ? 1 : 0;
+        a.max_norm = max_norm;
+        a.dynamic = dynamic ? 1 : 0;
+        a.growth = growth;
+        a.backoff = backoff;
+        a.interval = interval;
+        a.state = reinterpret_cast<ScaleState*>(state);
+        a.rec = reinterpret_cast<StepRecord*>(record);
+        a.table = reinterpret_cast<const float*>(table);
+        a.end = table_end;
+        a.filled = table_filled;
+        py::gil_scoped_release r;
+        scale_step(device, a, as_stream(stream));
+      },
+      py::arg("device"), py::arg("stream"), py::arg("recs"), py::arg("world"), py::arg("state"), py::arg("record"),
+      py::arg("table"), py::arg("table_end"), py::arg("table_filled"), py::arg("clip"), py::arg("max_norm"),
+      py::arg("dynamic"), py::arg("growth"), py::arg("backoff"), py::arg("interval"));
   h.def(
       "plan_coll",
       [](const std::string& op, const GridKnobs& k, int64_t n, int64_t es, int ranks_here) {
@@ -720,20 +757,20 @@ void bind_hip(py::module_& m) {
       .def(
           "step_adamw_shard",
           [](XgmiComm& c, uintptr_t gshard, uintptr_t coef, uintptr_t params, int64_t n, DType dt, uintptr_t stream,
-             uintptr_t mp, uintptr_t m1, uintptr_t m2, const AdamW& hp) {
+             uintptr_t mp, uintptr_t m1, uintptr_t m2, const AdamW& hp, bool record) {
             AdamShard st{reinterpret_cast<float*>(mp), reinterpret_cast<float*>(m1), reinterpret_cast<float*>(m2)};
             py::gil_scoped_release r;
             c.step_adamw_shard(reinterpret_cast<const float*>(gshard), reinterpret_cast<const float*>(coef),
-                               as_ptr(params), n, dt, as_stream(stream), st, hp);
+                               as_ptr(params), n, dt, as_stream(stream), st, hp, record);
           },
           py::arg("gshard"), py::arg("coef"), py::arg("params"), py::arg("n"), py::arg("dtype"), py::arg("stream"),
-          py::arg("master"), py::arg("exp_avg"), py::arg("exp_avg_sq"), py::arg("hyper"))
+          py::arg("master"), py::arg("exp_avg"), py::arg("exp_avg_sq"), py::arg("hyper"), py::arg("record") = false)
       .def_static(
           "step_adamw_shard_local",
           [](const std::vector<XgmiComm*>& comms, const std::vector<uintptr_t>& gshards,
              const std::vector<uintptr_t>& coefs, const std::vector<uintptr_t>& params, int64_t n, DType dt,
              uintptr_t stream, const std::vector<std::tuple<uintptr_t, uintptr_t, uintptr_t>>& states,
-             const AdamW& hp) {
+             const AdamW& hp, bool record) {
             std::vector<const float*> gs, cf;
             std::vector<void*> p;
             std::vector<AdamShard> st;
@@ -743,10 +780,10 @@ void bind_hip(py::module_& m) {
             for (auto& [a, b, c] : states)
               st.push_back({reinterpret_cast<float*>(a), reinterpret_cast<float*>(b), reinterpret_cast<float*>(c)});
             py::gil_scoped_release r;
-            XgmiComm::step_adamw_shard_local(comms, gs, cf, p, n, dt, as_stream(stream), st, hp);
+            XgmiComm::step_adamw_shard_local(comms, gs, cf, p, n, dt, as_stream(stream), st, hp, record);
           },
           py::arg("comms"), py::arg("gshards"), py::arg("coefs"), py::arg("params"), py::arg("n"), py::arg("dtype"),
-          py::arg("stream"), py::arg("states"), py::arg("hyper"))
+          py::arg("stream"), py::arg("states"), py::arg("hyper"), py::arg("record") = false)
       .def("block_elems", &XgmiComm::block_elems, py::arg("n"), py::arg("dtype"))
       .def(
           "collective",

@@ -4,7 +4,8 @@
 // the gradient scatter and parameter gather phases, adamw(), the fp32 state access forms and the
 // AdamW update of one reduce unit, which takes its gradient from one of two sources: the P-way
 // sum of the scattered chunks (fused step) or the fp32 shard the reduce-scatter half left, times
-// the clip coefficient (update half).
+// the clip coefficient (update half; in a loss-scaled step with coefficient and bias corrections
+// from the step record, RecordGrad).
 #pragma once
 
 #include "xgmi_device.h"
@@ -106,14 +107,23 @@ constexpr bool grad_fused(int w, int k) {
   return !((STREAM == 0 || STREAM == 3) && w == 1 && k < 2);
 }
 
+// AdamW's bias corrections of one launch: c1 = 1 - beta1^t, c2_sqrt = sqrt(1 - beta2^t). The
+// gradient source says where they come from (its corr()): the launch arguments, where the host
+// put them for its own step count, or the step record of a loss-scaled step, where the control
+// kernel put the host's values for the device's count (xgmi_scale.hip).
+struct BiasCorr {
+  float c1, c2_sqrt;
+};
+
 // AdamW (decoupled weight decay, PyTorch semantics) of one element; returns the new param.
-__device__ __forceinline__ float adamw(bool gf, float g, float* p, float* m, float* v, const CommArgs& a) {
+__device__ __forceinline__ float adamw(bool gf, float g, float* p, float* m, float* v, const CommArgs& a,
+                                       const BiasCorr& bc) {
   float pv = *p;
   pv *= 1.f - a.lr * a.wd;
   const float mv = moment(gf, a.beta1, *m, 1.f - a.beta1, g);
   const float vv = moment(gf, a.beta2, *v, (1.f - a.beta2) * g, g);
-  const float denom = sqrtf(vv) / a.c2_sqrt + a.eps;
-  pv -= (a.lr / a.c1) * mv / denom;
+  const float denom = sqrtf(vv) / bc.c2_sqrt + a.eps;
+  pv -= (a.lr / bc.c1) * mv / denom;
   // The callers round the returned value to the parameter dtype: it must be the fp32 value the
   // master holds. Left to itself the compiler folds the last multiply-subtract and the fp16
   // conversion of the scalar tail into one v_fma_mixlo_f16, which rounds the unrounded result
@@ -200,6 +210,7 @@ struct PeerSumGrad {
     for (int s = 0; s < P; ++s) g += ld_scalar_nt<E>(src.rsrc(s), t);
     return g;
   }
+  __device__ __forceinline__ BiasCorr corr(const CommArgs& a) const { return {a.c1, a.c2_sqrt}; }
 };
 
 // The update half of the clipped step: the unit's fp32 shard, read once (nt loads), mul = the
@@ -219,6 +230,17 @@ struct ShardGrad {
   }
   __device__ __forceinline__ void add_half(Acc8<E>& acc, int64_t e0) const { add4(acc.v, e0); }
   __device__ __forceinline__ float tail(int64_t t) const { return 0.f + ld_scalar_nt<F32>(rg, t); }
+  __device__ __forceinline__ BiasCorr corr(const CommArgs& a) const { return {a.c1, a.c2_sqrt}; }
+};
+
+// The update half of a loss-scaled step: the same shard, mul = the step record's coefficient
+// (clip / scale) and the corrections the record carries.
+template <class E>
+struct RecordGrad : ShardGrad<E> {
+  BiasCorr bc;
+  __device__ __forceinline__ RecordGrad(__amdgpu_buffer_rsrc_t rg_, const StepRecord& rec)
+      : ShardGrad<E>{rg_, rec.coef}, bc{rec.c1, rec.c2_sqrt} {}
+  __device__ __forceinline__ BiasCorr corr(const CommArgs&) const { return bc; }
 };
 
 // AdamW on `len` elements from `cstart` of rank r's shard (one reduce unit, one workgroup): the
@@ -238,6 +260,7 @@ __device__ __forceinline__ void adamw_unit(const CommArgs& a, int P, int r, int6
   float* const sv = a.opt_v[y] + cstart;
   const __amdgpu_buffer_rsrc_t rp = slab_rsrc(sp), rm = slab_rsrc(sm), rv = slab_rsrc(sv);
   const int64_t npk = len / EL;
+  const BiasCorr bc = grad.corr(a);
   if constexpr (STREAM == 3 && EL == 8) {
     // Run-contiguous halves (16-bit parameters, the default): lane l of a run of 256 packs
     // takes elements [4l, 4l + 4) of each half of the run's 2048 elements, so every fp32
@@ -279,10 +302,10 @@ __device__ __forceinline__ void adamw_unit(const CommArgs& a, int P, int r, int6
         for (int h = 0; h < 2; ++h) {
           const int64_t e0 = eoff(i, h);
           Acc8<E>& ac = acc[w][h];
-          ac.v[0] = adamw(grad_fused<STREAM>(w, 0), ac.v[0] * grad.mul, &p4[w][h].x, &m4[w][h].x, &v4[w][h].x, a);
-          ac.v[1] = adamw(grad_fused<STREAM>(w, 1), ac.v[1] * grad.mul, &p4[w][h].y, &m4[w][h].y, &v4[w][h].y, a);
-          ac.v[2] = adamw(grad_fused<STREAM>(w, 2), ac.v[2] * grad.mul, &p4[w][h].z, &m4[w][h].z, &v4[w][h].z, a);
-          ac.v[3] = adamw(grad_fused<STREAM>(w, 3), ac.v[3] * grad.mul, &p4[w][h].w, &m4[w][h].w, &v4[w][h].w, a);
+          ac.v[0] = adamw(grad_fused<STREAM>(w, 0), ac.v[0] * grad.mul, &p4[w][h].x, &m4[w][h].x, &v4[w][h].x, a, bc);
+          ac.v[1] = adamw(grad_fused<STREAM>(w, 1), ac.v[1] * grad.mul, &p4[w][h].y, &m4[w][h].y, &v4[w][h].y, a, bc);
+          ac.v[2] = adamw(grad_fused<STREAM>(w, 2), ac.v[2] * grad.mul, &p4[w][h].z, &m4[w][h].z, &v4[w][h].z, a, bc);
+          ac.v[3] = adamw(grad_fused<STREAM>(w, 3), ac.v[3] * grad.mul, &p4[w][h].w, &m4[w][h].w, &v4[w][h].w, a, bc);
           *reinterpret_cast<float4*>(sp + e0) = p4[w][h];
           *reinterpret_cast<float4*>(sm + e0) = m4[w][h];
           *reinterpret_cast<float4*>(sv + e0) = v4[w][h];
@@ -325,10 +348,10 @@ __device__ __forceinline__ void adamw_unit(const CommArgs& a, int P, int r, int6
 #pragma unroll
         for (int e = 0; e < EL / 4; ++e) {
           float* const g = acc[w].v + 4 * e;
-          g[0] = adamw(grad_fused<STREAM>(w, 0), g[0] * grad.mul, &p4[w][e].x, &m4[w][e].x, &v4[w][e].x, a);
-          g[1] = adamw(grad_fused<STREAM>(w, 1), g[1] * grad.mul, &p4[w][e].y, &m4[w][e].y, &v4[w][e].y, a);
-          g[2] = adamw(grad_fused<STREAM>(w, 2), g[2] * grad.mul, &p4[w][e].z, &m4[w][e].z, &v4[w][e].z, a);
-          g[3] = adamw(grad_fused<STREAM>(w, 3), g[3] * grad.mul, &p4[w][e].w, &m4[w][e].w, &v4[w][e].w, a);
+          g[0] = adamw(grad_fused<STREAM>(w, 0), g[0] * grad.mul, &p4[w][e].x, &m4[w][e].x, &v4[w][e].x, a, bc);
+          g[1] = adamw(grad_fused<STREAM>(w, 1), g[1] * grad.mul, &p4[w][e].y, &m4[w][e].y, &v4[w][e].y, a, bc);
+          g[2] = adamw(grad_fused<STREAM>(w, 2), g[2] * grad.mul, &p4[w][e].z, &m4[w][e].z, &v4[w][e].z, a, bc);
+          g[3] = adamw(grad_fused<STREAM>(w, 3), g[3] * grad.mul, &p4[w][e].w, &m4[w][e].w, &v4[w][e].w, a, bc);
           st_state<STREAM>(sp, rp, i * EL + 4 * e, p4[w][e]);
           st_state<STREAM>(sm, rm, i * EL + 4 * e, m4[w][e]);
           st_state<STREAM>(sv, rv, i * EL + 4 * e, v4[w][e]);
@@ -345,7 +368,7 @@ __device__ __forceinline__ void adamw_unit(const CommArgs& a, int P, int r, int6
   }
   const int64_t t = npk * EL + threadIdx.x;
   if (t < len) {
-    const float pv = adamw(false, grad.tail(t) * grad.mul, sp + t, sm + t, sv + t, a);
+    const float pv = adamw(false, grad.tail(t) * grad.mul, sp + t, sm + t, sv + t, a, bc);
     Scalar<E>::store(own_out, t, pv);
     for (int k = 0; k < P; ++k)
       if (k != r) st_scalar_wt<E>(slab_rsrc(a.base[k] + roff), t, pv);

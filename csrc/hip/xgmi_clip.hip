@@ -16,6 +16,10 @@
 //                      the write-through pushes to every peer) and gather. `coef` is one fp32 the
 //                      host side computed on the device from every rank's sum of squares.
 //
+//                      In its record mode (template parameter REC, the loss-scaled step) coef,
+//                      AdamW's bias corrections and a skip word come from the StepRecord the
+//                      step-control kernel (xgmi_scale.hip) wrote between the halves.
+//
 // Between the two, 8 B per owned parameter go through HBM that the fused step keeps in
 // registers (4 written, 4 read), and one 16-byte all-gather carries the ranks' sums.
 //
@@ -233,14 +237,45 @@ __global__ __launch_bounds__(kCommThreads) void rs_sq_kernel(CommArgs a) {
 // The update half: phases 2 and 3 of the fused step through the same adamw_unit and
 // gather_params (xgmi_adam_device.h), with the fp32 shard times the clip coefficient as the
 // gradient. tests/test_clip_gpu.py holds the two gradient sources bit for bit against each other.
-template <class E, int STREAM, int U>
+//
+// REC (the loss-scaled step, xgmi_scale.hip): a.coef[y] points at the rank's StepRecord. The
+// coefficient and AdamW's two bias corrections come from it instead of the launch arguments, and
+// its skip word decides whether the launch updates anything. The record was written by the
+// control kernel earlier on the same stream and is read with plain loads; it is uniform over the
+// launch, and it has the same bits on every rank (the control kernels add the same records in the
+// same order), so every rank takes the same branch.
+//
+// A skipped launch writes no master, moment or parameter, no R slot of a peer, and gathers
+// nothing: the reduce units and the copy out of the R slots are left out. It still walks the whole
+// flag protocol - the entry guard, the epoch-e flag of every reduce unit to every peer, the wait
+// for every peer's flags, the last workgroup's "launch e done" - and that is on purpose. Every
+// kernel of a communicator leans on one invariant (entry_guard, xgmi_device.h): a rank that has
+// completed launch e has seen epoch-e flags from every peer, so every peer has entered e and
+// finished every launch before it; "only the previous launch's reads can still be pending" is
+// that sentence. A skipped launch that left through the finish path alone would complete
+// without hearing from anyone: after rs_sq at e - 1 (kHazS = e - 1) and a skipped e, the next
+// reduce-scatter half at e + 1 finds kHazS != e and pushes unguarded into S slots a slower peer
+// is still reducing in e - 1; the low-latency kernel's parity slots of e and e + 2 would meet the
+// same way. Carrying the hazard words forward could mend the first case and not the second. With
+// the protocol walked, a skipped launch is to every other kernel an ordinary update half that
+// happened to move no data: epoch, ticket, kHazR and the flag rows end exactly as after a clean
+// one (kHazR is recorded although no R slot was read: a poll of one local word per peer at most).
+// The flags of a skipped launch promise R data that was never pushed; only the same launch's
+// gather could take them, and it reads no slot. Cost: the flag round trip, about the latency
+// of an empty launch of this grid.
+template <class E, int STREAM, int U, bool REC>
 __global__ __launch_bounds__(kCommThreads) void adamw_shard_kernel(CommArgs a) {
   constexpr int es = 16 / E::ELEMS;
   const StepCtx k(a, a.P);
   const int y = blockIdx.y;
   const int r = k.r;
   const float* const gshard = a.gshard[y];
-  const float coef = *a.coef[y];
+  StepRecord rec{};
+  if constexpr (REC)
+    rec = *reinterpret_cast<const StepRecord*>(a.coef[y]);
+  else
+    rec.coef = *a.coef[y];
+  const bool skip = REC && rec.skip != 0;  // uniform
 
   // AdamW on the owned shard, push the new parameters (phase 2 of the fused step). The pushes
   // go into R slots the peers may still be reading in the previous launch: entry guard.
@@ -248,13 +283,26 @@ __global__ __launch_bounds__(kCommThreads) void adamw_shard_kernel(CommArgs a) {
   if (k.P > 1 && static_cast<int>(blockIdx.x) < nu2) entry_guard(a, k.ctl, r, k.epoch, kHazR, -1, k.deadline, k.err);
   for (int u = blockIdx.x; u < nu2; u += k.G) {
     const OwnUnit o = own_unit(a, r, u);
-    if (o.len > 0 && unit_in_bounds(a, o.cstart * es, o.len * es, u, k.err))
-      adamw_unit<E, STREAM, U>(a, k.P, r, o.cstart, o.len, ShardGrad<E>{slab_rsrc(gshard + o.cstart), coef});
+    if (!skip && o.len > 0 && unit_in_bounds(a, o.cstart * es, o.len * es, u, k.err)) {
+      if constexpr (REC)
+        adamw_unit<E, STREAM, U>(a, k.P, r, o.cstart, o.len, RecordGrad<E>(slab_rsrc(gshard + o.cstart), rec));
+      else
+        adamw_unit<E, STREAM, U>(a, k.P, r, o.cstart, o.len, ShardGrad<E>{slab_rsrc(gshard + o.cstart), rec.coef});
+    }
     publish_flags([&](int p) -> uint32_t* { return p == r ? nullptr : f2(a, p, r, u); }, k.P, k.epoch, k.rel);
   }
 
-  // Gather the other owners' updated parameter chunks (phase 3 of the fused step)
-  gather_params<E>(a, k, a.out[y]);
+  // Gather the other owners' updated parameter chunks (phase 3 of the fused step); a skipped
+  // launch only waits for their flags
+  if (skip) {
+    for (int u = blockIdx.x; u < k.nu; u += k.G) {
+      const PeerUnit p = peer_unit(a, k, u);
+      wait_flags([&](int q) -> const uint32_t* { return f2(a, k.r, p.j, p.c * a.sub + q); }, a.sub, k.epoch,
+                 k.deadline, k.err, ERR_TIMEOUT_REDUCE, k.acq);
+    }
+  } else {
+    gather_params<E>(a, k, a.out[y]);
+  }
   finish_launch_done(a, k.ctl, k.epoch, r, kHazR);  // peers may still gather from R
 }
 
@@ -284,15 +332,27 @@ void launch_rs_sq(const CommArgs& a, dim3 grid, hipStream_t s, DType dt, bool ac
   });
 }
 
-void launch_adamw_shard(const CommArgs& a, dim3 grid, hipStream_t s, DType dt) {
+namespace {
+
+template <bool REC>
+void launch_adamw_shard_mode(const CommArgs& a, dim3 grid, hipStream_t s, DType dt) {
   dispatch_dtype(static_cast<int>(dt), [&](auto tag) {
     using E = decltype(tag);
     // 16-bit parameters: run-contiguous halves; fp32: the generic body, plain state access
     if constexpr (E::ELEMS == 8)
-      hipLaunchKernelGGL((adamw_shard_kernel<E, 3, 2>), grid, dim3(kCommThreads), 0, s, a);
+      hipLaunchKernelGGL((adamw_shard_kernel<E, 3, 2, REC>), grid, dim3(kCommThreads), 0, s, a);
     else
-      hipLaunchKernelGGL((adamw_shard_kernel<E, 0, 2>), grid, dim3(kCommThreads), 0, s, a);
+      hipLaunchKernelGGL((adamw_shard_kernel<E, 0, 2, REC>), grid, dim3(kCommThreads), 0, s, a);
   });
+}
+
+}  // namespace
+
+void launch_adamw_shard(const CommArgs& a, dim3 grid, hipStream_t s, DType dt, bool record) {
+  if (record)
+    launch_adamw_shard_mode<true>(a, grid, s, dt);
+  else
+    launch_adamw_shard_mode<false>(a, grid, s, dt);
 }
 
 }  // namespace mxar

@@ -359,8 +359,41 @@ static void set_adamw_hyper(CommArgs& a, const AdamW& h) {
   a.beta2 = h.beta2;
   a.eps = h.eps;
   a.wd = h.weight_decay;
-  a.c1 = 1.f - std::pow(h.beta1, static_cast<float>(h.step));
-  a.c2_sqrt = std::sqrt(1.f - std::pow(h.beta2, static_cast<float>(h.step)));
+  adamw_corrections(h.beta1, h.beta2, h.step, &a.c1, &a.c2_sqrt);
+}
+
+void adamw_corrections(float beta1, float beta2, int step, float* c1, float* c2_sqrt) {
+  *c1 = 1.f - std::pow(beta1, static_cast<float>(step));
+  *c2_sqrt = std::sqrt(1.f - std::pow(beta2, static_cast<float>(step)));
+}
+
+int adamw_corrections_end(float beta1, float beta2, int cap) {
+  auto ones = [&](int t) {
+    float c1, c2;
+    adamw_corrections(beta1, beta2, t, &c1, &c2);
+    return c1 == 1.f && c2 == 1.f;
+  };
+  if (!ones(cap)) return cap;
+  int lo = 0, hi = cap;  // ones(hi), not ones(lo) (count 0 is never applied); beta^t is monotone
+  while (hi - lo > 1) {
+    const int mid = lo + (hi - lo) / 2;
+    (ones(mid) ? hi : lo) = mid;
+  }
+  return hi;
+}
+
+void scale_step(int device, const ScaleStepArgs& a, hipStream_t stream) {
+  if (a.recs == nullptr || a.state == nullptr || a.rec == nullptr || a.table == nullptr)
+    throw std::invalid_argument("scale_step: null buffer");
+  if ((reinterpret_cast<uintptr_t>(a.recs) | reinterpret_cast<uintptr_t>(a.state) | reinterpret_cast<uintptr_t>(a.rec)) & 15)
+    throw std::invalid_argument("scale_step: records, state and step record must be 16-byte aligned");
+  if (a.P < 1 || a.P > kMaxRanks) throw std::invalid_argument("scale_step: world out of range");
+  if (a.end < 1 || a.filled < 1 || a.filled > a.end)
+    throw std::invalid_argument("scale_step: the correction table needs 1 <= filled <= end");
+  if (a.dynamic && a.interval < 1) throw std::invalid_argument("scale_step: growth_interval counts from 1");
+  hip_check(hipSetDevice(device), "hipSetDevice");
+  launch_scale_step(a, stream);
+  hip_check(hipGetLastError(), "scale_step launch");
 }
 
 // One launch for the ranks `group` (all on one device, consecutive rank ids starting at
@@ -597,7 +630,8 @@ void XgmiComm::reduce_scatter_sq(const void* grads, float* gshard, float* sq, in
 void XgmiComm::step_adamw_shard_local(const std::vector<XgmiComm*>& group, const std::vector<const float*>& gshards,
                                       const std::vector<const float*>& coefs, const std::vector<void*>& params,
                                       int64_t n, DType dt, hipStream_t stream, const std::vector<AdamShard>& st,
-                                      const AdamW& h) {
+                                      const AdamW& h, bool record) {
+  const int64_t coef_bytes = record ? static_cast<int64_t>(sizeof(StepRecord)) : 4;
   if (group.empty() || gshards.size() != group.size() || coefs.size() != group.size() ||
       params.size() != group.size() || st.size() != group.size())
     throw std::invalid_argument("step_adamw_shard: one gshard / coef / params / shard state per rank");
@@ -608,16 +642,17 @@ void XgmiComm::step_adamw_shard_local(const std::vector<XgmiComm*>& group, const
          reinterpret_cast<uintptr_t>(st[y].param) | reinterpret_cast<uintptr_t>(st[y].exp_avg) |
          reinterpret_cast<uintptr_t>(st[y].exp_avg_sq)) & 15)
       throw std::invalid_argument("step_adamw_shard: buffers must be 16-byte aligned");
-    if (coefs[y] == nullptr || (reinterpret_cast<uintptr_t>(coefs[y]) & 3))
-      throw std::invalid_argument("step_adamw_shard: coef must be a 4-byte aligned fp32");
-    if (overlaps(gshards[y], shard_bytes, params[y], n * es) || overlaps(coefs[y], 4, params[y], n * es))
+    if (coefs[y] == nullptr || (reinterpret_cast<uintptr_t>(coefs[y]) & (record ? 15 : 3)))
+      throw std::invalid_argument(record ? "step_adamw_shard: the step record must be 16-byte aligned"
+                                         : "step_adamw_shard: coef must be a 4-byte aligned fp32");
+    if (overlaps(gshards[y], shard_bytes, params[y], n * es) || overlaps(coefs[y], coef_bytes, params[y], n * es))
       throw std::invalid_argument("step_adamw_shard: gshard, coef and params must not overlap");
     for (const float* s : {st[y].param, st[y].exp_avg, st[y].exp_avg_sq})
-      if (overlaps(s, shard_bytes, gshards[y], shard_bytes) || overlaps(s, shard_bytes, coefs[y], 4))
+      if (overlaps(s, shard_bytes, gshards[y], shard_bytes) || overlaps(s, shard_bytes, coefs[y], coef_bytes))
         throw std::invalid_argument("step_adamw_shard: the shard state must not overlap gshard or coef");
   }
   if (n <= 0) return;
-  if (h.step < 1) throw std::invalid_argument("step_adamw_shard: step counts from 1");
+  if (!record && h.step < 1) throw std::invalid_argument("step_adamw_shard: step counts from 1");
   dim3 grid;
   CommArgs a = shard_step_args(group, n, dt, "step_adamw_shard", stream, &grid);
   TraceScope span("xgmi", [&] {
@@ -632,8 +667,8 @@ void XgmiComm::step_adamw_shard_local(const std::vector<XgmiComm*>& group, const
     a.opt_m[y] = st[y].exp_avg;
     a.opt_v[y] = st[y].exp_avg_sq;
   }
-  set_adamw_hyper(a, h);
-  launch_adamw_shard(a, grid, stream, dt);
+  set_adamw_hyper(a, h);  // record: c1 / c2_sqrt are set and not read
+  launch_adamw_shard(a, grid, stream, dt, record);
   hip_check(hipGetLastError(), "adamw_shard launch");
   for (XgmiComm* c : group) {
     ++c->stats_.launches;
@@ -642,8 +677,8 @@ void XgmiComm::step_adamw_shard_local(const std::vector<XgmiComm*>& group, const
 }
 
 void XgmiComm::step_adamw_shard(const float* gshard, const float* coef, void* params, int64_t n, DType dt,
-                                hipStream_t stream, const AdamShard& st, const AdamW& h) {
-  step_adamw_shard_local({this}, {gshard}, {coef}, {params}, n, dt, stream, {st}, h);
+                                hipStream_t stream, const AdamShard& st, const AdamW& h, bool record) {
+  step_adamw_shard_local({this}, {gshard}, {coef}, {params}, n, dt, stream, {st}, h, record);
 }
 
 void XgmiComm::allreduce(const void* in, void* out, int64_t n, DType dt, hipStream_t stream, Algo algo, float scale) {

@@ -49,6 +49,15 @@ struct AdamShard {
   float* exp_avg_sq = nullptr;
 };
 
+// AdamW's bias corrections at step t as every step of this project applies them: fp32, the
+// host's std::pow. c1 = 1 - beta1^t, c2_sqrt = sqrt(1 - beta2^t).
+void adamw_corrections(float beta1, float beta2, int step, float* c1, float* c2_sqrt);
+// The first count from which both corrections are exactly 1.0f (they never leave it again: beta^t
+// only shrinks), or `cap` when that lies beyond it.
+int adamw_corrections_end(float beta1, float beta2, int cap);
+// The loss-scaled step's control kernel (xgmi_scale.hip) on `device`, stream-ordered.
+void scale_step(int device, const ScaleStepArgs& a, hipStream_t stream);
+
 struct CommStats {
   uint64_t calls = 0, launches = 0, bytes = 0, oneshot = 0, twoshot = 0, ring = 0, threshold = 0, ll = 0, coll = 0,
            adamw = 0, stream_switches = 0;
@@ -266,12 +275,15 @@ class XgmiComm {
                                       DType dt, hipStream_t stream, float scale, bool accumulate = false);
   // step_adamw_shard: AdamW on the shard state with gshard[i] * *coef as the gradient (coef: a
   // device fp32), the updated parameters all-gathered into `params` [n] as step_adamw does.
+  // record (the loss-scaled step, xgmi_scale.hip): `coef` points at a 16-byte aligned StepRecord
+  // instead - coefficient, bias corrections and skip word come from it, h.step is not used, and a
+  // launch whose record says skip writes nothing (it still takes part in the flag protocol).
   void step_adamw_shard(const float* gshard, const float* coef, void* params, int64_t n, DType dt,
-                        hipStream_t stream, const AdamShard& st, const AdamW& h);
+                        hipStream_t stream, const AdamShard& st, const AdamW& h, bool record = false);
   static void step_adamw_shard_local(const std::vector<XgmiComm*>& comms, const std::vector<const float*>& gshards,
                                      const std::vector<const float*>& coefs, const std::vector<void*>& params,
                                      int64_t n, DType dt, hipStream_t stream, const std::vector<AdamShard>& st,
-                                     const AdamW& h);
+                                     const AdamW& h, bool record = false);
 
   // Collectives on [P][m] buffers (m elements per block, m * dtype a multiple of 16 B):
   //   AllToAll      in[P][m] -> out[P][m]   out_r[s] = in_s[r]

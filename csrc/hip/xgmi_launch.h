@@ -30,7 +30,10 @@ void launch_adamw(const CommArgs& a, dim3 grid, hipStream_t s, DType dt);
 // shard with the sum of squares; AdamW from the shard times the clip coefficient + all-gather.
 // accumulate: gshard += the scaled sum (fp32, product rounded before the add) instead of =
 void launch_rs_sq(const CommArgs& a, dim3 grid, hipStream_t s, DType dt, bool accumulate);
-void launch_adamw_shard(const CommArgs& a, dim3 grid, hipStream_t s, DType dt);
+// record: a.coef[y] points at a StepRecord (coefficient, skip word, bias corrections)
+void launch_adamw_shard(const CommArgs& a, dim3 grid, hipStream_t s, DType dt, bool record = false);
+// Host entry of the loss-scaled step's one-wave control kernel (xgmi_scale.hip).
+void launch_scale_step(const ScaleStepArgs& a, hipStream_t s);
 // Host entry of all-to-all (mode 0) / all-gather (1) / reduce-scatter (2) (xgmi_coll.hip).
 void launch_coll(const CommArgs& a, dim3 grid, hipStream_t s, DType dt, int mode);
 // Host entry of the rooted broadcast / reduce, root = a.root (xgmi_rooted.hip).

@@ -11,6 +11,15 @@ Step times, alternating in one call:
             package, so the checkout needs this tree's Python API (reduce_scatter_sq with
             `accumulate`, clip_coef, step_adamw_shard); an older one fails in the child.
 
+--loss-scale adds two variants of this tree to the alternation:
+  scaled    the clean loss-scaled + clipped step: reduce_scatter_sq + loss_scale_step (the
+            records' all-gather and the one-wave control kernel, csrc/hip/xgmi_scale.hip) +
+            step_adamw_record; a static scale of 1024, so nothing drifts over the rounds
+  skipped   the same launches with an inf among the sums of squares: the update half walks its
+            flag protocol and moves no data
+With --parent the summary then also holds `scaled_vs_parent_clipped`: this tree's clean
+loss-scaled step over the parent's clipped step, and whether it is inside the parent's margin.
+
 Every round times `iters` steps of each variant in turn with device events; the figure of a
 variant is the median over rounds of the round's median. Byte model per owned parameter: fused
 14 B read + 14 B written, clipped 8 B more (the fp32 shard written and read once). With
@@ -71,7 +80,7 @@ def measure(args, variants):
     grads = [fill_uniform(torch.empty(n, dtype=dtype, device=dev), seed=10 + k) for k in range(P)]
     params = [fill_uniform(torch.empty(n, dtype=dtype, device=dev), seed=1) for _ in range(P)]
     states = [{k: torch.zeros(b, device=dev) for k in ("master", "exp_avg", "exp_avg_sq")} for _ in range(P)]
-    gshards = [torch.zeros(b, device=dev) for _ in range(P)] if "clipped" in variants else None
+    gshards = [torch.zeros(b, device=dev) for _ in range(P)] if set(variants) - {"fused"} else None
     step = [0]
 
     def fused():
@@ -85,6 +94,25 @@ def measure(args, variants):
         cl.step_adamw_shard(gshards, params, states, coef=coef, step=step[0], **HP)
 
     fns = {"fused": fused, "clipped": clipped}
+    if "scaled" in variants or "skipped" in variants:
+        from akka_allreduce_1_amd.parallel import loss_scale as LS
+
+        cfg = LS.LossScaleConfig(1024.0)
+        table = LS.CorrectionTable(dev, HP["betas"])
+        ls_states = [LS.new_state(cfg, dev) for _ in range(P)]
+        records = [torch.zeros(LS.REC_WORDS, device=dev) for _ in range(P)]
+        inf = [torch.full((1,), float("inf"), device=dev) for _ in range(P)]
+        bound = [0]
+
+        def scaled(sq_override=None):
+            bound[0] += 1
+            table.ensure(bound[0])
+            sqs = cl.reduce_scatter_sq(grads, gshards)
+            cl.loss_scale_step(sq_override or sqs, ls_states, records, [table] * P, cfg, 1.0)
+            cl.step_adamw_record(gshards, params, states, records=records, **HP)
+
+        fns["scaled"] = scaled
+        fns["skipped"] = lambda: scaled(inf)
     for v in variants:
         for _ in range(args.warmup):
             fns[v]()
@@ -163,6 +191,7 @@ def main() -> int:
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--parent", default=None, help="another built checkout (with this tree's Python API) whose steps are timed or digested too")
     ap.add_argument("--digest", action="store_true", help="compare result digests with --parent instead of timing")
+    ap.add_argument("--loss-scale", action="store_true", help="time the clean loss-scaled step and a skipped step too")
     ap.add_argument("--out", default=None)
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -187,11 +216,12 @@ def main() -> int:
                 json.dump(dict(summary, here=here, parent=there), f, indent=1)
         return 1 if differ or len(there) != len(here) else 0
     res = {"clipped": [], "fused": [], "parent": [], "parent_clipped": []}
+    mine = ["clipped", "fused"] + (["scaled", "skipped"] if args.loss_scale else [])
     passes = 3 if args.parent else 1
     for _ in range(passes):  # this tree and the parent take turns
-        here = measure(args, ["clipped", "fused"])
-        res["clipped"] += here["clipped"]
-        res["fused"] += here["fused"]
+        here = measure(args, mine)
+        for v in mine:
+            res.setdefault(v, []).extend(here[v])
         if args.parent:
             there = _child(os.path.abspath(args.parent),
                            ["--ranks", str(args.ranks), "--n", str(args.n), "--dtype", args.dtype, "--grid",
@@ -214,6 +244,10 @@ def main() -> int:
         margin = {v: (max(res[p]) - min(res[p])) / statistics.median(res[p]) for v, p in pairs.items()}
         summary["margin"] = {v: round(m, 4) for v, m in margin.items()}
         summary["within_margin"] = {v: med[v] <= med[p] * (1 + margin[v]) for v, p in pairs.items()}
+        if args.loss_scale:
+            summary["scaled_vs_parent_clipped"] = {
+                "ratio": round(med["scaled"] / med["parent_clipped"], 4),
+                "within_margin": med["scaled"] <= med["parent_clipped"] * (1 + margin["clipped"])}
     print(json.dumps(summary), flush=True)
     if args.out:
         with open(args.out, "w") as f:
