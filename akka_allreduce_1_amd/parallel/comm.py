@@ -157,6 +157,19 @@ def gather_sq_records(comm, rec: torch.Tensor) -> torch.Tensor:
     return out.view(torch.float64).view(comm.world, 2)
 
 
+def _adamw_hyper(lr: float, betas: tuple[float, float], eps: float, weight_decay: float, step: int):
+    """The hyper-parameter struct of the fused AdamW launches. A record-driven update half takes its
+    bias corrections from the step record and gets `step` = 1."""
+    h = _H.AdamW()
+    h.lr, (h.beta1, h.beta2), h.eps, h.weight_decay, h.step = lr, betas, eps, weight_decay, step
+    return h
+
+
+def _state_ptrs(state: dict) -> tuple[int, int, int]:
+    """(master, exp_avg, exp_avg_sq): the addresses of a rank's fp32 shard state (see `adamw_state`)."""
+    return state["master"].data_ptr(), state["exp_avg"].data_ptr(), state["exp_avg_sq"].data_ptr()
+
+
 def _check_scale_buffers(state: torch.Tensor, record: torch.Tensor, device) -> None:
     if state.dtype != torch.int32 or state.numel() != 4 or not state.is_contiguous() or state.device != device:
         raise ValueError(f"loss-scale state must be a contiguous int32 [4] tensor on {device}")
@@ -662,11 +675,9 @@ class XgmiCommunicator:
         if grads.numel() != params.numel() or grads.dtype != params.dtype:
             raise ValueError("grads and params must match in size and dtype")
         self._step_grid(grid)
-        h = _H.AdamW()
-        h.lr, (h.beta1, h.beta2), h.eps, h.weight_decay, h.step = lr, betas, eps, weight_decay, step
         self._c.step_adamw(grads.data_ptr(), params.data_ptr(), params.numel(), _dtype_code(params.dtype),
-                           _current_stream(self._dev), state["master"].data_ptr(), state["exp_avg"].data_ptr(),
-                           state["exp_avg_sq"].data_ptr(), h, 1.0 / self.world if op == "avg" else 1.0)
+                           _current_stream(self._dev), *_state_ptrs(state),
+                           _adamw_hyper(lr, betas, eps, weight_decay, step), 1.0 / self.world if op == "avg" else 1.0)
         return params
 
     def _step_grid(self, grid: int) -> None:
@@ -687,6 +698,10 @@ class XgmiCommunicator:
         """Scratch for the clipped step: the fp32 gradient shard of `params` (shard_len elements)."""
         return torch.zeros(self.shard_len(params.numel(), params.dtype), dtype=torch.float32, device=self.device)
 
+    def _check_gshard(self, gshard: torch.Tensor, full: torch.Tensor) -> None:
+        if gshard.dtype != torch.float32 or gshard.numel() != self.shard_len(full.numel(), full.dtype):
+            raise ValueError("gshard must hold shard_len(n) fp32 elements")
+
     def reduce_scatter_sq(self, grads: torch.Tensor, gshard: torch.Tensor, *, op: str = "avg",
                           grid: int = 0, accumulate: bool = False) -> torch.Tensor:
         """First half of the clipped step, one launch: reduce-scatter `grads` (mean by default;
@@ -698,8 +713,7 @@ class XgmiCommunicator:
         returns the sum of the squares of the new values."""
         if op not in ("sum", "avg"):
             raise ValueError(f"unsupported op {op!r}")
-        if gshard.dtype != torch.float32 or gshard.numel() != self.shard_len(grads.numel(), grads.dtype):
-            raise ValueError("gshard must hold shard_len(n) fp32 elements")
+        self._check_gshard(gshard, grads)
         if not (grads.is_contiguous() and gshard.is_contiguous()):
             raise ValueError("tensors must be contiguous")
         self._step_grid(grid)
@@ -722,16 +736,20 @@ class XgmiCommunicator:
         """Second half of the clipped step, one launch: AdamW on this rank's shard state with
         `gshard[i] * coef` as the gradient (`coef`: a 1-element fp32 device tensor), then the
         all-gather of the new `params` - the fused step from its optimizer on."""
-        if coef.dtype != torch.float32 or coef.numel() != 1 or coef.get_device() != self._dev:
-            raise ValueError(f"coef must be a 1-element fp32 tensor on {self.device}")
-        if gshard.dtype != torch.float32 or gshard.numel() != self.shard_len(params.numel(), params.dtype):
-            raise ValueError("gshard must hold shard_len(n) fp32 elements")
+        return self._update_half(gshard, params, state, coef, False, _adamw_hyper(lr, betas, eps, weight_decay, step),
+                                 grid)
+
+    def _update_half(self, gshard: torch.Tensor, params: torch.Tensor, state: dict, src: torch.Tensor, record: bool,
+                     hyper, grid: int) -> torch.Tensor:
+        """The update half's launch. `src`: the coefficient, or with `record` the step record."""
+        if src.dtype != torch.float32 or src.numel() != (8 if record else 1) or src.get_device() != self._dev:
+            raise ValueError(f"record must be an 8-element fp32 tensor on {self.device}" if record else
+                             f"coef must be a 1-element fp32 tensor on {self.device}")
+        self._check_gshard(gshard, params)
         self._step_grid(grid)
-        h = _H.AdamW()
-        h.lr, (h.beta1, h.beta2), h.eps, h.weight_decay, h.step = lr, betas, eps, weight_decay, step
-        self._c.step_adamw_shard(gshard.data_ptr(), coef.data_ptr(), params.data_ptr(), params.numel(),
-                                 _dtype_code(params.dtype), _current_stream(self._dev), state["master"].data_ptr(),
-                                 state["exp_avg"].data_ptr(), state["exp_avg_sq"].data_ptr(), h)
+        self._c.step_adamw_shard(gshard.data_ptr(), src.data_ptr(), params.data_ptr(), params.numel(),
+                                 _dtype_code(params.dtype), _current_stream(self._dev), *_state_ptrs(state), hyper,
+                                 record=record)
         return params
 
     # -------------------------------------------- the loss-scaled step (csrc/hip/xgmi_scale.hip)
@@ -755,17 +773,8 @@ class XgmiCommunicator:
         corrections come from it, and when its skip word is set the launch writes nothing - not
         the shard state, not `params`, not a peer's slot - while it still takes part in the flag
         protocol (csrc/hip/xgmi_clip.hip), so any launch may follow on every rank."""
-        if record.dtype != torch.float32 or record.numel() != 8 or record.get_device() != self._dev:
-            raise ValueError(f"record must be an 8-element fp32 tensor on {self.device}")
-        if gshard.dtype != torch.float32 or gshard.numel() != self.shard_len(params.numel(), params.dtype):
-            raise ValueError("gshard must hold shard_len(n) fp32 elements")
-        self._step_grid(grid)
-        h = _H.AdamW()
-        h.lr, (h.beta1, h.beta2), h.eps, h.weight_decay, h.step = lr, betas, eps, weight_decay, 1
-        self._c.step_adamw_shard(gshard.data_ptr(), record.data_ptr(), params.data_ptr(), params.numel(),
-                                 _dtype_code(params.dtype), _current_stream(self._dev), state["master"].data_ptr(),
-                                 state["exp_avg"].data_ptr(), state["exp_avg_sq"].data_ptr(), h, record=True)
-        return params
+        return self._update_half(gshard, params, state, record, True, _adamw_hyper(lr, betas, eps, weight_decay, 1),
+                                 grid)
 
     def shard_len(self, n: int, dtype: torch.dtype) -> int:
         """Elements of the block a rank owns in a fused step over n elements."""
@@ -1023,17 +1032,15 @@ class LocalCluster:
                    lr: float, betas: tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
                    weight_decay: float = 0.0, step: int, op: str = "avg") -> None:
         """The fused reduce-scatter + AdamW + all-gather for every logical rank."""
-        h = _H.AdamW()
-        h.lr, (h.beta1, h.beta2), h.eps, h.weight_decay, h.step = lr, betas, eps, weight_decay, step
+        h = _adamw_hyper(lr, betas, eps, weight_decay, step)
         n = params[0].numel()
         code = _dtype_code(params[0].dtype)
         for g in self.groups:
             dev = self.devices[g[0]]
             _H.XgmiComm.step_adamw_local(
                 [self.comms[k] for k in g], [grads[k].data_ptr() for k in g], [params[k].data_ptr() for k in g], n,
-                code, torch.cuda.current_stream(dev).cuda_stream,
-                [(states[k]["master"].data_ptr(), states[k]["exp_avg"].data_ptr(), states[k]["exp_avg_sq"].data_ptr())
-                 for k in g], h, 1.0 / self.world if op == "avg" else 1.0)
+                code, torch.cuda.current_stream(dev).cuda_stream, [_state_ptrs(states[k]) for k in g], h,
+                1.0 / self.world if op == "avg" else 1.0)
 
     def reduce_scatter_sq(self, grads: Sequence[torch.Tensor], gshards: Sequence[torch.Tensor], *,
                           op: str = "avg", accumulate: bool = False) -> list[torch.Tensor]:
@@ -1067,44 +1074,45 @@ class LocalCluster:
         """sqs[k]: rank k's sum of squares, or its list of them in bucket order. Every rank's
         16-byte record goes through the all-gather kernel; returns (total_norms, coefs), one 0-d
         fp32 tensor per rank (see XgmiCommunicator.clip_coef)."""
-        recs = [sq_record(s) for s in sqs]
-        if self.world == 1:
-            outs = recs
-        else:
-            outs = self.collective("all_gather", [r.view(torch.float32) for r in recs])
-        res = [clip_coef_from_records(o.view(torch.float64).view(self.world, 2), max_norm) for o in outs]
+        res = [clip_coef_from_records(o, max_norm) for o in self._gather_sq_records(sqs)]
         return [r[0] for r in res], [r[1] for r in res]
+
+    def _gather_sq_records(self, sqs: Sequence) -> list[torch.Tensor]:
+        """One `sq_record` per rank through the all-gather kernel: every rank's float64 [world, 2]."""
+        outs = [sq_record(s) for s in sqs]
+        if self.world > 1:
+            outs = self.collective("all_gather", [r.view(torch.float32) for r in outs])
+        return [o.view(torch.float64).view(self.world, 2) for o in outs]
 
     def step_adamw_shard(self, gshards: Sequence[torch.Tensor], params: Sequence[torch.Tensor],
                          states: Sequence[dict], *, coef: Sequence[torch.Tensor], lr: float,
                          betas: tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
                          step: int) -> None:
         """Second half of the clipped step for every logical rank; coef[k]: rank k's coefficient."""
-        h = _H.AdamW()
-        h.lr, (h.beta1, h.beta2), h.eps, h.weight_decay, h.step = lr, betas, eps, weight_decay, step
+        self._update_half(gshards, params, states, coef, False, _adamw_hyper(lr, betas, eps, weight_decay, step))
+
+    def _update_half(self, gshards, params, states, srcs, record: bool, hyper) -> None:
+        """The update half's launches. srcs[k]: rank k's coefficient, or with `record` its step record."""
         n = params[0].numel()
         code = _dtype_code(params[0].dtype)
         self._check_shards(params, gshards, n, code)
         for k in range(self.world):
-            if coef[k].dtype != torch.float32 or coef[k].numel() != 1 or coef[k].device != self.devices[k]:
-                raise ValueError(f"rank {k}: coef must be a 1-element fp32 tensor on {self.devices[k]}")
+            s = srcs[k]
+            if s.dtype != torch.float32 or s.numel() != (8 if record else 1) or s.device != self.devices[k]:
+                what = "record must be an 8-element" if record else "coef must be a 1-element"
+                raise ValueError(f"rank {k}: {what} fp32 tensor on {self.devices[k]}")
         for g in self.groups:
             dev = self.devices[g[0]]
             _H.XgmiComm.step_adamw_shard_local(
-                [self.comms[k] for k in g], [gshards[k].data_ptr() for k in g], [coef[k].data_ptr() for k in g],
+                [self.comms[k] for k in g], [gshards[k].data_ptr() for k in g], [srcs[k].data_ptr() for k in g],
                 [params[k].data_ptr() for k in g], n, code, torch.cuda.current_stream(dev).cuda_stream,
-                [(states[k]["master"].data_ptr(), states[k]["exp_avg"].data_ptr(), states[k]["exp_avg_sq"].data_ptr())
-                 for k in g], h)
+                [_state_ptrs(states[k]) for k in g], hyper, record=record)
 
     def loss_scale_step(self, sqs: Sequence, states: Sequence[torch.Tensor], records: Sequence[torch.Tensor],
                         tables: Sequence, cfg, max_norm: float | None = None) -> None:
         """The control kernel of the loss-scaled step for every logical rank, each on its own
         state, record and table (see XgmiCommunicator.loss_scale_step)."""
-        recs = [sq_record(s) for s in sqs]
-        if self.world == 1:
-            outs = recs
-        else:
-            outs = self.collective("all_gather", [r.view(torch.float32) for r in recs])
+        outs = self._gather_sq_records(sqs)
         for k in range(self.world):
             _check_scale_buffers(states[k], records[k], self.devices[k])
             with torch.cuda.device(self.devices[k]):
@@ -1116,21 +1124,7 @@ class LocalCluster:
                           betas: tuple[float, float] = (0.9, 0.999), eps: float = 1e-8,
                           weight_decay: float = 0.0) -> None:
         """The record-driven update half for every logical rank; records[k]: rank k's step record."""
-        h = _H.AdamW()
-        h.lr, (h.beta1, h.beta2), h.eps, h.weight_decay, h.step = lr, betas, eps, weight_decay, 1
-        n = params[0].numel()
-        code = _dtype_code(params[0].dtype)
-        self._check_shards(params, gshards, n, code)
-        for k in range(self.world):
-            if records[k].dtype != torch.float32 or records[k].numel() != 8 or records[k].device != self.devices[k]:
-                raise ValueError(f"rank {k}: record must be an 8-element fp32 tensor on {self.devices[k]}")
-        for g in self.groups:
-            dev = self.devices[g[0]]
-            _H.XgmiComm.step_adamw_shard_local(
-                [self.comms[k] for k in g], [gshards[k].data_ptr() for k in g], [records[k].data_ptr() for k in g],
-                [params[k].data_ptr() for k in g], n, code, torch.cuda.current_stream(dev).cuda_stream,
-                [(states[k]["master"].data_ptr(), states[k]["exp_avg"].data_ptr(), states[k]["exp_avg_sq"].data_ptr())
-                 for k in g], h, record=True)
+        self._update_half(gshards, params, states, records, True, _adamw_hyper(lr, betas, eps, weight_decay, 1))
 
     def barrier(self) -> None:
         for g in self.groups:

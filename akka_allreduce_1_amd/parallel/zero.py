@@ -120,6 +120,7 @@ class _Bucket:
         self.params: list[torch.nn.Parameter] = []
         self.offsets: list[int] = []
         self.numel = 0
+        self.nbytes = 0
         self.flat_param: torch.Tensor | None = None
         self.flat_grad: torch.Tensor | None = None
         self.grad_shard: torch.Tensor | None = None
@@ -156,30 +157,30 @@ class ShardedDataParallel:
         self.rank = int(getattr(comm, "rank"))
         self.device = self.params[0].device
         self.on_gpu = self.device.type == "cuda"
-        self.overlap = overlap and self.on_gpu
         self.stream = comm_stream(self.device) if self.on_gpu else None
         self.buckets = self._build(bucket_bytes)
         self.slot_of = {id(p): (b, off) for b in self.buckets for p, off in zip(b.params, b.offsets)}
         self.fused = dict(fused_adamw) if fused_adamw is not None else None
-        # the fused step is split where a global decision has to be known before any parameter moves
-        self._split = self.max_grad_norm is not None or self._scale_cfg is not None
-        if self.fused is not None:
-            self.fused["grid"] = int(comm_grid)
+        # what has to be known over all buckets before any parameter moves: the scale rule (which clips too), the
+        # clip coefficient, or nothing. A fused step that decides is split into two halves per bucket (_in_halves)
+        self._decide = "scale" if self._scale_cfg is not None else "clip" if self.max_grad_norm is not None else None
+        # overlap: a bucket is launched from its last gradient hook, on the side stream. The one-launch fused step
+        # has no reduce half to overlap: there only step_in_backward launches from the hooks
+        one_launch = self.fused is not None and self._decide is None
+        self.overlap = bool(step_in_backward if one_launch else overlap) and self.on_gpu
+        self.step_in_backward = bool(step_in_backward) and self.on_gpu
         self.adamw_states: list[dict] = []
         self._t = 0
         if self.fused is not None:
+            self.fused["grid"] = int(comm_grid)
             if not hasattr(comm, "step_adamw"):
                 raise ValueError("fused_adamw needs a communicator with step_adamw (XgmiCommunicator)")
             cap = comm.world * comm.slot_bytes
             for b in self.buckets:
-                if b.numel * b.flat_param.element_size() > cap:
+                if b.nbytes > cap:
                     raise ValueError(f"fused_adamw: bucket of {b.numel} elements exceeds world * slot_bytes = {cap} B")
             self.adamw_states = [comm.adamw_state(b.flat_param) for b in self.buckets]
-            # without step_in_backward the fused launch runs in step(); with it, from the hooks.
-            # Clipped: the reduce-scatter half may run from the hooks, the update half in step()
-            if not self._split:
-                self.overlap = bool(step_in_backward) and self.on_gpu
-            if self._split or self.grad_accumulation:
+            if self._decide is not None or self.grad_accumulation:
                 if not hasattr(comm, "step_adamw_shard"):
                     raise ValueError("fused_adamw with max_grad_norm, grad_accumulation or loss_scale needs a "
                                      "communicator with step_adamw_shard")
@@ -195,12 +196,13 @@ class ShardedDataParallel:
             if self.grad_accumulation:  # scratch, not in state_dict(): fp32 sums over micro-batches
                 self._accs = [torch.zeros(b.grad_shard.numel(), dtype=torch.float32, device=self.device)
                               for b in self.buckets]
-        self.step_in_backward = self.fused is not None and self.overlap and not self._split
         self.last_grad_norm = torch.zeros((), dtype=torch.float32, device=self.device)
         self.last_clip_coef = torch.ones((), dtype=torch.float32, device=self.device)
         if self._scale_cfg is not None:
             self._init_loss_scale()
-        self._t_started = False
+        self._t_started = False  # the one-launch step of this backward has taken its step number
+        self._folding = False  # inside accumulate()
+        self._side_used = False  # the side stream holds launches the current stream has not joined
         self._hooks = [p.register_post_accumulate_grad_hook(self._on_grad) for p in self.params]
         self._next = 0
         self.stats = {"steps": 0, "reduce_scatter_bytes": 0, "all_gather_bytes": 0, "clip_bytes": 0}
@@ -229,6 +231,7 @@ class ShardedDataParallel:
             es = torch.empty(0, dtype=b.dtype).element_size()
             unit = self.world * max(1, _ALIGN_BYTES // es)  # every shard 16-B sized and aligned
             b.numel = (b.numel + unit - 1) // unit * unit
+            b.nbytes = b.numel * es  # of the flat gradient and of the flat parameter: what a collective over it moves
             b.flat_param = torch.zeros(b.numel, dtype=b.dtype, device=self.device)
             b.flat_grad = torch.zeros(b.numel, dtype=b.dtype, device=self.device)
             for p, off in zip(b.params, b.offsets):
@@ -261,121 +264,111 @@ class ShardedDataParallel:
             self._reduce(self.buckets[self._next])
             self._next += 1
 
-    def _fused_bucket(self, b: _Bucket) -> None:
-        if not self._t_started:  # first bucket of this backward: a new optimizer step
-            self._t += 1
-            self._t_started = True
-        st = self.adamw_states[b.index]
-        self.stream.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(self.stream):
-            self.comm.step_adamw(b.flat_grad, b.flat_param, st, step=self._t, **self.fused)
-        b.launched = True
-        self.stats["reduce_scatter_bytes"] += b.flat_grad.numel() * b.flat_grad.element_size()
-        self.stats["all_gather_bytes"] += b.flat_param.numel() * b.flat_param.element_size()
-
-    def _rs_sq_bucket(self, b: _Bucket) -> None:
-        """Split fused step, first half of a bucket: reduce-scatter into gshard + sum of squares.
-        The first micro-batch of a step overwrites gshard, later ones add into it."""
-        acc = self.micro_batches > 0
-
-        def launch():
-            self._sqs[b.index] = self.comm.reduce_scatter_sq(b.flat_grad, self.gshards[b.index], op="avg",
-                                                             grid=self.fused["grid"], accumulate=acc)
-        if self.overlap:
+    def _launch(self, side: bool, launch: Callable[[], None]) -> None:
+        """`launch()` on the side stream, behind what the current stream holds so far, when `side`;
+        else on the current stream. The caller says which: the split step's reduce halves go aside
+        when `overlap`, the unfused reduce-scatter whenever there is a GPU (`on_gpu`), the one-launch
+        fused step exactly when it is launched in backward."""
+        if side:
             self.stream.wait_stream(torch.cuda.current_stream(self.device))
             with torch.cuda.stream(self.stream):
                 launch()
+            self._side_used = True
         else:
             launch()
-        b.launched = True
-        self.stats["reduce_scatter_bytes"] += b.flat_grad.numel() * b.flat_grad.element_size()
-        if acc:
-            self.stats["clip_bytes"] += 4 * self.gshards[b.index].numel()  # the old sum, read back
+
+    def _in_halves(self) -> bool:
+        """Whether this backward's fused launches are the halves of the split step (reduce-scatter
+        into gshard + squares; later coefficient, update + gather) and not the one-launch step: where
+        a decision over all buckets precedes the update, and for every micro-batch of an accumulated
+        step - gshard is the accumulator. A step without accumulate() stays the one-launch step."""
+        return self._decide is not None or self._folding or self.micro_batches > 0
 
     def _reduce(self, b: _Bucket) -> None:
-        if self.fused is not None:
-            # grad_accumulation, unclipped: only accumulate() and a step() that follows one get here
-            if self._split or self.grad_accumulation:
-                self._rs_sq_bucket(b)
-            else:
-                self._fused_bucket(b)
-            return
-        if self.on_gpu:
-            self.stream.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.stream(self.stream):
-                self.comm.reduce_scatter(b.flat_grad, b.grad_shard, op="avg")
+        """Bucket b's launch for this backward: the reduce-scatter, or all of the one-launch step."""
+        if self.fused is None:
+            self._launch(self.on_gpu, lambda: self.comm.reduce_scatter(b.flat_grad, b.grad_shard, op="avg"))
+        elif self._in_halves():
+            self._launch(self.overlap, lambda: self._rs_sq_half(b))
         else:
-            self.comm.reduce_scatter(b.flat_grad, b.grad_shard, op="avg")
+            if not self._t_started:  # first bucket of this backward: a new optimizer step
+                self._t += 1
+                self._t_started = True
+            self._launch(self.step_in_backward, lambda: self.comm.step_adamw(
+                b.flat_grad, b.flat_param, self.adamw_states[b.index], step=self._t, **self.fused))
+            self.stats["all_gather_bytes"] += b.nbytes
         b.launched = True
-        self.stats["reduce_scatter_bytes"] += b.flat_grad.numel() * b.flat_grad.element_size()
+        self.stats["reduce_scatter_bytes"] += b.nbytes
 
-    # ------------------------------------------------------------------ step API
-    def step(self) -> None:
-        """Finish the gradient reduce-scatter, update the local shards, all-gather the
-        parameters (call after backward)."""
-        if self.step_in_backward:
-            self._launch_ready(all_=True)  # buckets whose parameters got no gradient
-            torch.cuda.current_stream(self.device).wait_stream(self.stream)
-            self._rearm()
-            self._t_started = False
-            self.stats["steps"] += 1
-            return
-        if self.fused is not None and (self._split or self.micro_batches > 0):
-            # the split step: clipped, loss-scaled, or the last micro-batch of an accumulated step
-            self._launch_ready(all_=True)
-            if self.overlap:
-                torch.cuda.current_stream(self.device).wait_stream(self.stream)
-            if self._scale_cfg is not None:
-                self._scaled_update_halves()
-                self._rearm()
-                self.micro_batches = 0
-                self.stats["steps"] += 1
-                return
-            if self.max_grad_norm is not None:
-                self.last_grad_norm, self.last_clip_coef = self.comm.clip_coef(self._sqs, self.max_grad_norm)
-                coef = self.last_clip_coef
-            else:
-                coef = self._one
+    def _rs_sq_half(self, b: _Bucket) -> None:
+        """First half of the split step: reduce-scatter into gshard + sum of squares. The first
+        micro-batch of a step overwrites gshard, later ones add into it."""
+        gs, acc = self.gshards[b.index], self.micro_batches > 0
+        self._sqs[b.index] = self.comm.reduce_scatter_sq(b.flat_grad, gs, op="avg", grid=self.fused["grid"],
+                                                         accumulate=acc)
+        if acc:
+            self.stats["clip_bytes"] += 4 * gs.numel()  # the old sum, read back
+
+    def _update_halves(self) -> None:
+        """What the split step decides - the control kernel on the gathered sums of squares
+        (loss-scaled), the clip coefficient, or the constant 1.0 of a merely accumulated step - then
+        every bucket's update half: AdamW on gshard * coef and the all-gather. Loss-scaled, the half
+        takes coefficient, bias corrections and skip word from the record, and a skipped one writes
+        nothing (its bytes are counted all the same)."""
+        if self._decide == "scale":
+            self._applied_bound += 1
+            self._table.ensure(self._applied_bound)
+            self.comm.loss_scale_step(self._sqs, self._scale_state, self._record, self._table, self._scale_cfg,
+                                      self.max_grad_norm)
+            update, how = self.comm.step_adamw_record, {"record": self._record}
+        else:
+            coef = self._one
+            if self._decide == "clip":
+                self.last_grad_norm, coef = self.comm.clip_coef(self._sqs, self.max_grad_norm)
+                self.last_clip_coef = coef
             self._t += 1
-            for b, st, gs in zip(self.buckets, self.adamw_states, self.gshards):
-                self.comm.step_adamw_shard(gs, b.flat_param, st, coef=coef, step=self._t, **self.fused)
-                self.stats["all_gather_bytes"] += b.flat_param.numel() * b.flat_param.element_size()
-                self.stats["clip_bytes"] += 8 * gs.numel()  # the fp32 shard: written once, read once
-            self._rearm()
-            self.micro_batches = 0
-            self.stats["steps"] += 1
-            return
-        if self.fused is not None:
-            self._t += 1
-            for b, st in zip(self.buckets, self.adamw_states):
-                self.comm.step_adamw(b.flat_grad, b.flat_param, st, step=self._t, **self.fused)
-                self.stats["reduce_scatter_bytes"] += b.flat_grad.numel() * b.flat_grad.element_size()
-                self.stats["all_gather_bytes"] += b.flat_param.numel() * b.flat_param.element_size()
-            self._rearm()
-            self.stats["steps"] += 1
-            return
-        self._launch_ready(all_=True)
-        if self.on_gpu:
-            torch.cuda.current_stream(self.device).wait_stream(self.stream)
-        if self.micro_batches > 0:
+            update, how = self.comm.step_adamw_shard, {"coef": coef, "step": self._t}
+        for b, st, gs in zip(self.buckets, self.adamw_states, self.gshards):
+            update(gs, b.flat_param, st, **how, **self.fused)
+            self.stats["all_gather_bytes"] += b.nbytes
+            self.stats["clip_bytes"] += 8 * gs.numel()  # the fp32 shard: written once, read once
+
+    def _torch_update(self) -> None:
+        """The unfused update: grad_shard receives what the optimizer is to see - the folded sum,
+        scaled where something is decided - then the optimizer runs on the shards and every bucket's
+        shard is all-gathered. A skipped step (loss-scaled, non-finite) stops after the decision."""
+        folded = self.micro_batches > 0
+        if folded:
             self._add_shards()
-        if self._scale_cfg is not None:
-            if self._unscale_shards():  # the one host sync of the unfused path: torch optimizers cannot skip on the device
-                self._rearm()
-                self.micro_batches = 0
-                self.stats["steps"] += 1
+        if self._decide is not None:
+            if self._scale_shards():
                 return
-        elif self.max_grad_norm is not None:
-            self._clip_shards()
-        elif self.micro_batches > 0:
+        elif folded:
             for b, acc in zip(self.buckets, self._accs):
                 b.grad_shard.copy_(acc)
         self.optimizer.step()
         for b in self.buckets:
             # the shard is part of the gather's output buffer: gather from a copy
-            src = b.shard_param.detach().clone()
-            self.comm.all_gather(src, b.flat_param)
-            self.stats["all_gather_bytes"] += b.flat_param.numel() * b.flat_param.element_size()
+            self.comm.all_gather(b.shard_param.detach().clone(), b.flat_param)
+            self.stats["all_gather_bytes"] += b.nbytes
+
+    # ------------------------------------------------------------------ step API
+    def _finish_backward(self) -> None:
+        """Launch what the hooks have not - buckets whose parameters got no gradient included - and
+        let the current stream join the side stream where this backward used it."""
+        self._launch_ready(all_=True)
+        if self._side_used:
+            torch.cuda.current_stream(self.device).wait_stream(self.stream)
+            self._side_used = False
+
+    def step(self) -> None:
+        """Finish the gradient reduce-scatter, update the local shards, all-gather the
+        parameters (call after backward)."""
+        self._finish_backward()
+        if self.fused is None:
+            self._torch_update()
+        elif self._in_halves():
+            self._update_halves()  # else the one-launch step: its buckets have just been launched, or were in backward
         self._rearm()
         self.micro_batches = 0
         self.stats["steps"] += 1
@@ -385,6 +378,7 @@ class ShardedDataParallel:
             b.pending = len(b.params)
             b.launched = False
         self._next = 0
+        self._t_started = self._folding = False
 
     def accumulate(self) -> None:
         """End a micro-batch that is not the last of its optimizer step (call after its backward;
@@ -395,9 +389,8 @@ class ShardedDataParallel:
         gradient hooks. Needs `grad_accumulation=True`."""
         if not self.grad_accumulation:
             raise RuntimeError("accumulate() needs ShardedDataParallel(..., grad_accumulation=True)")
-        self._launch_ready(all_=True)
-        if self.on_gpu:
-            torch.cuda.current_stream(self.device).wait_stream(self.stream)
+        self._folding = True  # the fused launches of this backward fold into gshard (_in_halves)
+        self._finish_backward()
         if self.fused is None:
             self._add_shards()
         for b in self.buckets:
@@ -414,20 +407,33 @@ class ShardedDataParallel:
             else:
                 acc.add_(b.grad_shard.float())
 
-    def _clip_shards(self) -> None:
-        """Unfused clipping: this rank's sum of squares over its gradient shards (fp32, bucket
-        order), the ranks' sums all-gathered and added in rank order, every shard scaled. After
-        accumulate(): the squares of the fp32 sums over micro-batches, and `grad_shard` receives
-        (sum * coef) rounded once to the parameter dtype."""
-        srcs = self._accs if self.micro_batches > 0 else [b.grad_shard.float() for b in self.buckets]
+    def _scale_shards(self) -> bool:
+        """The unfused decision: this rank's sum of squares over its gradient shards (fp32, bucket
+        order; after accumulate() over the fp32 sums of the micro-batches), the ranks' sums
+        all-gathered and added in rank order, the rule - clip_coef_from_records, or
+        loss_scale.scale_step_rule with coef = clip / scale - and, unless the step is skipped,
+        every shard times coef (after accumulate(): `grad_shard` receives sum * coef, rounded once
+        to the parameter dtype). Returns whether the step is skipped: loss-scaled, that is the one
+        host sync of the unfused path - torch optimizers cannot skip on the device."""
+        folded = self.micro_batches > 0
+        srcs = self._accs if folded else [b.grad_shard.float() for b in self.buckets]
         sqs = [s.pow(2).sum() for s in srcs]
         recs = gather_sq_records(self.comm, sq_record(sqs))
-        self.last_grad_norm, self.last_clip_coef = clip_coef_from_records(recs, self.max_grad_norm)
+        if self._decide == "clip":
+            self.last_grad_norm, coef = clip_coef_from_records(recs, self.max_grad_norm)
+            self.last_clip_coef = coef
+        else:
+            self.last_grad_norm, self.last_clip_coef, coef, found = _ls.scale_step_rule(
+                recs, self._scale_state, self._scale_cfg, self.max_grad_norm)
+            self.last_step_skipped = found.to(torch.int32)
+            if bool(found):
+                return True
         for b, s in zip(self.buckets, srcs):
-            if self.micro_batches > 0:
-                b.grad_shard.copy_(s * self.last_clip_coef)
+            if folded:
+                b.grad_shard.copy_(s * coef)
             else:
-                b.grad_shard.mul_(self.last_clip_coef)
+                b.grad_shard.mul_(coef)
+        return False
 
     # ------------------------------------------------------------------ loss scaling
     def _init_loss_scale(self) -> None:
@@ -454,37 +460,6 @@ class ShardedDataParallel:
         if self._scale_cfg is None:
             raise RuntimeError("scale_loss() needs ShardedDataParallel(..., loss_scale=...)")
         return loss * self.loss_scale
-
-    def _scaled_update_halves(self) -> None:
-        """Fused, loss-scaled: the control kernel on the gathered sums of squares, then every
-        bucket's record-driven update half (a skipped one writes nothing)."""
-        self._applied_bound += 1
-        self._table.ensure(self._applied_bound)
-        self.comm.loss_scale_step(self._sqs, self._scale_state, self._record, self._table, self._scale_cfg,
-                                  self.max_grad_norm)
-        for b, st, gs in zip(self.buckets, self.adamw_states, self.gshards):
-            self.comm.step_adamw_record(gs, b.flat_param, st, record=self._record, **self.fused)
-            self.stats["all_gather_bytes"] += b.flat_param.numel() * b.flat_param.element_size()
-            self.stats["clip_bytes"] += 8 * gs.numel()
-
-    def _unscale_shards(self) -> bool:
-        """Unfused, loss-scaled: the sums of squares as `_clip_shards` takes them, the rule
-        (loss_scale.scale_step_rule), and - unless the step is skipped - every shard times
-        coef = clip / scale, rounded once. Returns whether the step is skipped (one host sync)."""
-        srcs = self._accs if self.micro_batches > 0 else [b.grad_shard.float() for b in self.buckets]
-        sqs = [s.pow(2).sum() for s in srcs]
-        recs = gather_sq_records(self.comm, sq_record(sqs))
-        self.last_grad_norm, self.last_clip_coef, coef, found = _ls.scale_step_rule(
-            recs, self._scale_state, self._scale_cfg, self.max_grad_norm)
-        self.last_step_skipped = found.to(torch.int32)
-        if bool(found):
-            return True
-        for b, s in zip(self.buckets, srcs):
-            if self.micro_batches > 0:
-                b.grad_shard.copy_(s * coef)
-            else:
-                b.grad_shard.mul_(coef)
-        return False
 
     # ------------------------------------------------------------------ checkpoint / resume
     def state_dict(self) -> dict:
